@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched DIYGym step path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload ur_high_5] [--envs-per-gpu 16384]
+    python bench.py --gpus N --steps K --warmup W [--workload ur_high_5] [--envs-per-gpu 16384] [--dump-outputs DIR] [--full]
+
+A plain run builds the world, runs W untimed warm-up steps (plus one untimed replay of every graph it captured), times
+exactly K steps, writes what the last timed step returned (--dump-outputs) and prints the result line.  Everything else
+described below (roofline, solver statistics, aged segment, eager API rates, extra legs, CPU baseline, rocprofv3 child
+runs) is measured only with --full.
 
 One "step" = one DIYGym.step() over the whole batch: controller addons (batched
 IK for ur_high_5) -> one 1/240 s physics step (2 substeps, <=150 PGS iterations)
@@ -21,7 +26,7 @@ contract asks for.  ``python bench.py --gpus N`` WITHOUT torchrun's environment
 spawns the N ranks itself (the parent never touches a GPU); under
 ``python -m torch.distributed.run`` it is a rank.
 
-Rank 0 prints ONE JSON line (schema in the task statement) with extra objects:
+Rank 0 prints ONE JSON line (schema in the task statement); with --full it carries extra objects:
 ``roofline`` (dominant kernel timed live with HIP events on the launch stream and, at N=1, by rocprofv3 child runs of
 this command that also collect the HBM / SQ counters -- ``--no-pmc`` opts out),
 ``solver`` (live Gauss-Seidel / IK iteration statistics from the kernel's
@@ -254,6 +259,41 @@ def cpu_baseline(cfg, act_dim, lo, hi, seconds=4.0):
             'fp32_1_core': f32_1, 'fp32_all_cores': f32_n, 'fp64_all_cores': f64_n, 'pybullet': pyb,
             'sample': 'same config, random actions, ~%.0f s each: C oracle built as fp32 on 1 core (64 envs), fp32 with OpenMP over envs on %d cores (%d envs) '
                       '[= value], fp64 on %d cores; pybullet itself: %s' % (seconds, cores, 64 * cores, cores, pyb['status'])}
+
+
+DUMP_BUDGET = 63 * 10**6   # bytes of array data --dump-outputs may write: with the .npy headers, under 64 MB
+
+
+def dump_outputs(leg, outdir, budget=DUMP_BUDGET):
+    """--dump-outputs: what the timed path handed its caller after its last step -- the output buffers of dg_world_step
+    after the masked reset (observations, rewards, terminals, collapsed reward / terminal flag) and, for camera workloads,
+    the images dg_world_render wrote -- one float32 ``<name>.npy`` per buffer, env-major.  When all of them together exceed
+    `budget` bytes, every file holds the same fixed, seeded sample of env rows (sorted), and ``env_index.npy`` (float64)
+    says which.  Returns {name: shape}."""
+    import numpy as np
+    torch, sim, B = leg.torch, leg.sim, leg.B
+    arrays = [('obs', sim.obs), ('reward', sim.rew), ('terminal', sim.term), ('reward_sum', sim.rew_sum), ('terminal_flag', sim.term_flag)]
+    for k, cam in enumerate(leg.cameras):
+        for part, t in zip(('rgb', 'depth', 'segmentation'), cam._buffers):
+            if t is not None:
+                arrays.append(('camera%d_%s' % (k, part), t))
+    per_env = sum(4 * (t.numel() // B) for _, t in arrays)
+    idx = None
+    if per_env * B > budget:
+        keep = max(1, budget // (per_env + 8))
+        idx = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays:
+        if idx is not None:
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(outdir, name + '.npy'), a)
+        shapes[name] = list(a.shape)
+    if idx is not None:
+        np.save(os.path.join(outdir, 'env_index.npy'), idx.astype(np.float64))
+        shapes['env_index'] = [len(idx)]
+    return shapes
 
 
 def quantiles(t):
@@ -678,9 +718,10 @@ def run_rank(args, argv):
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     distributed = world > 1
+    full = args.full
 
     pmc = None
-    if not args.no_pmc and not distributed:
+    if full and not args.no_pmc and not distributed:
         pmc = profile_children(args, argv)  # child processes; this process has not touched the GPU yet
 
     torch.cuda.set_device(local_rank)
@@ -722,15 +763,18 @@ def run_rank(args, argv):
         return el
 
     elapsed = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(main, args.dump_outputs)
     episodes_main = float(sim.state[1, :B].sum().item()) - B  # DG_ST_EPISODE summed over envs
-    step_ms, render_ms, step_eager_ms = main.kernel_times(max(R, min(64, args.steps)))
-    solver = main.solver_stats() if rank == 0 else None
+    if full:
+        step_ms, render_ms, step_eager_ms = main.kernel_times(max(R, min(64, args.steps)))
+    solver = main.solver_stats() if full and rank == 0 else None
 
     # (measured BEFORE the aged segment, so that the rates are those of the API on the same young rollout as `value`)
     # eager public-API rates: env.step() with the reference's dict actions, and with flatten_actions /
     # flatten_observations + collapsed reward / terminal (the trainer-facing fast path); auto-reset as above
     api = None
-    if rank == 0 and not args.no_api:
+    if full and rank == 0 and not args.no_api:
         from diy_gym_amd.utils import unflatten
         n_api = 100
         dict_ring = [unflatten(r, env.action_space, batch_dims=1) for r in ring] if main.lo.numel() else [{} for _ in ring]
@@ -769,7 +813,7 @@ def run_rank(args, argv):
 
     # aged segment: the same loop after --age-steps more (untimed) steps of the same random-action rollout
     aged = None
-    if args.age_steps > 0:
+    if full and args.age_steps > 0:
         main.run((args.age_steps // R) * R)
         main.eager(args.age_steps % R)
         el = timed(args.steps)
@@ -783,14 +827,6 @@ def run_rank(args, argv):
     if rank == 0:
         total_envs = B * world
         value = total_envs * args.steps / elapsed
-        kms_events = render_ms if main.kernel_name == 'render_kernel' else step_ms
-        roof = roofline_of(main, kms_events, step_ms, render_ms, step_eager_ms, pmc.get('main') if pmc else None)
-        roof['survey_bytes_per_env_step'] = 449 if args.workload.startswith('ur_high_5') else None
-        roof['limiter'] = ('NOT HBM either: VALU issue of the culling and intersection tests around 655 MB of image writes per launch (DESIGN.md 6)' if args.workload == 'from_the_readme' else
-                           'NOT HBM: instruction issue and latency of one wavefront per SIMD; the hbm fraction is reported because the contract asks for it')
-        roof['pmc_source'] = ('rocprofv3 child runs of this command, this invocation (%.0f s)' % pmc['seconds']) if pmc else None
-        if main.cameras and render_ms > step_ms * 0.2 and args.workload != 'from_the_readme':
-            roof['note'] = 'camera render takes %.2f ms of the step' % render_ms
         out = {
             'metric': 'env steps/sec (whole node)', 'value': value, 'unit': 'env-steps/s', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
@@ -799,32 +835,42 @@ def run_rank(args, argv):
                        'timestep': 1.0 / 240.0, 'substeps': env.layout.substeps, 'solver_iteration_cap': int(env.builder.solver_iterations),
                        'solver_start': {k: env.builder.params[k] for k in ('motor_guess', 'limit_guess', 'warmstart', 'warmstart_friction')},
                        'narrow_phase': {k: env.builder.params[k] for k in ('hull_contacts', 'hull_margin', 'contact_margin')},
-                       'auto_reset': auto_reset, 'timed_path': 'backend entry points dg_world_step%s + dg_world_reset(term_flag); env.step() rates are in api_eager' % (' + dg_world_render' if main.cameras else ''),
+                       'auto_reset': auto_reset, 'timed_path': 'backend entry points dg_world_step%s + dg_world_reset(term_flag); env.step() rates are in api_eager (--full)' % (' + dg_world_render' if main.cameras else ''),
                        'launch': ('one hipGraph of the %d timed steps' % args.steps if main.graph_whole is not None else 'hipGraph replay of %d-step segments' % R) if main.graph is not None else 'eager',
                        'untimed_steps_before_the_timed_region': untimed,
                        'episodes_finished_rank0': episodes_main, 'parallelism': 'independent env shards x%d, no collective' % world,
                        'envs_per_wavefront': sim.lanes, 'lds_bytes_per_workgroup': sim.lds_bytes,
                        'parity': 'vs the C oracle only; parity with pybullet itself is UNPINNED (DESIGN.md 4)'},
-            'roofline': roof, 'solver': solver, 'aged': aged, 'api_eager': api,
         }
+        if full:
+            kms_events = render_ms if main.kernel_name == 'render_kernel' else step_ms
+            roof = roofline_of(main, kms_events, step_ms, render_ms, step_eager_ms, pmc.get('main') if pmc else None)
+            roof['survey_bytes_per_env_step'] = 449 if args.workload.startswith('ur_high_5') else None
+            roof['limiter'] = ('NOT HBM either: VALU issue of the culling and intersection tests around 655 MB of image writes per launch (DESIGN.md 6)' if args.workload == 'from_the_readme' else
+                               'NOT HBM: instruction issue and latency of one wavefront per SIMD; the hbm fraction is reported because the contract asks for it')
+            roof['pmc_source'] = ('rocprofv3 child runs of this command, this invocation (%.0f s)' % pmc['seconds']) if pmc else None
+            if main.cameras and render_ms > step_ms * 0.2 and args.workload != 'from_the_readme':
+                roof['note'] = 'camera render takes %.2f ms of the step' % render_ms
+            out.update({'roofline': roof, 'solver': solver, 'aged': aged, 'api_eager': api})
         main.close()
-        # the other tail of the headline scene, the reference's solver settings, the other BASELINE configs (N = 1 default run)
-        t_legs = time.time()
-        for name in leg_names(args):
-            try:
-                rec = measure_leg(name, device, args, pmc.get(name) if pmc else None)
-            except Exception as exc:  # pragma: no cover
-                rec = {'error': repr(exc)}
-            if name in CONFIG_LEGS or name not in DEFAULT_LEGS:
-                out.setdefault('configs', {})[name] = rec
-            else:
-                out[name] = rec
-                if 'ms_per_step' in rec:
-                    rec['ms_per_step_over_young'] = rec['ms_per_step'] / out['ms_per_step']
-        if leg_names(args):
-            out['legs_seconds'] = round(time.time() - t_legs, 1)
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(cfg, main.lo.numel(), main.lo, main.hi)
+        if full:
+            # the other tail of the headline scene, the reference's solver settings, the other BASELINE configs (N = 1 --full run)
+            t_legs = time.time()
+            for name in leg_names(args):
+                try:
+                    rec = measure_leg(name, device, args, pmc.get(name) if pmc else None)
+                except Exception as exc:  # pragma: no cover
+                    rec = {'error': repr(exc)}
+                if name in CONFIG_LEGS or name not in DEFAULT_LEGS:
+                    out.setdefault('configs', {})[name] = rec
+                else:
+                    out[name] = rec
+                    if 'ms_per_step' in rec:
+                        rec['ms_per_step_over_young'] = rec['ms_per_step'] / out['ms_per_step']
+            if leg_names(args):
+                out['legs_seconds'] = round(time.time() - t_legs, 1)
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(cfg, main.lo.numel(), main.lo, main.hi)
         print(json.dumps(out), flush=True)
     if distributed:
         dist.barrier()
@@ -838,17 +884,21 @@ def main():
     ap.add_argument('--warmup', type=int, default=50)
     ap.add_argument('--workload', default='ur_high_5', choices=sorted(WORKLOADS))
     ap.add_argument('--envs-per-gpu', type=int, default=None, help='default: the size BASELINE.json quotes for the workload')
-    ap.add_argument('--age-steps', type=int, default=4000, help='untimed steps before the second (aged) timed segment; 0 disables it')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last one returned as DIR/<name>.npy '
+                    '(float32, rank 0, at most 64 MB: a fixed seeded sample of envs beyond that)')
+    ap.add_argument('--full', action='store_true', help='also measure everything besides the headline: roofline (with rocprofv3 child runs at N=1), '
+                    'solver statistics, the aged segment, eager API rates, the extra legs and the CPU baseline')
+    ap.add_argument('--age-steps', type=int, default=4000, help='--full: untimed steps before the second (aged) timed segment; 0 disables it')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-auto-reset', action='store_true')
-    ap.add_argument('--no-api', action='store_true', help='skip the eager env.step() API measurements')
+    ap.add_argument('--no-api', action='store_true', help='--full: skip the eager env.step() API measurements')
     ap.add_argument('--eager', action='store_true', help='time the eager launch loop instead of a replayed hipGraph')
-    ap.add_argument('--pmc', action='store_true', help='(default at N=1; kept for old command lines)')
-    ap.add_argument('--no-pmc', action='store_true', help='N=1: skip the rocprofv3 child runs (kernel trace + HBM / SQ counter passes) that fill roofline.traffic / kernel_ms')
+    ap.add_argument('--pmc', action='store_true', help='(default with --full at N=1; kept for old command lines)')
+    ap.add_argument('--no-pmc', action='store_true', help='--full, N=1: skip the rocprofv3 child runs (kernel trace + HBM / SQ counter passes) that fill roofline.traffic / kernel_ms')
     ap.add_argument('--pmc-budget', type=int, default=420, help='seconds the rocprofv3 child runs may take in total')
     ap.add_argument('--inner', action='store_true', help=argparse.SUPPRESS)  # the profiled child: eager loops of every leg, nothing else
     ap.add_argument('--manifest', default=None, help=argparse.SUPPRESS)
-    ap.add_argument('--legs', default='all', help="extra legs of the default N=1 ur_high_5 run: 'all', 'none' or a comma-separated subset of " + ','.join(LEGS))
+    ap.add_argument('--legs', default='all', help="extra legs of the --full N=1 ur_high_5 run: 'all', 'none' or a comma-separated subset of " + ','.join(LEGS))
     ap.add_argument('--master-port', type=int, default=0)
     ap.add_argument('--selftest-launcher', action='store_true', help='CPU-only rendezvous test of the N-rank launcher (gloo)')
     args = ap.parse_args()

@@ -10,7 +10,7 @@ OUT=gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 trace() {  # name, bench args...
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$name -- python3 bench.py "$@" --no-pmc --no-cpu-baseline --no-api --legs none > $OUT/bench_$name.json 2> $OUT/trace_$name.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$name -- python3 bench.py "$@" --full --no-pmc --no-cpu-baseline --no-api --legs none > $OUT/bench_$name.json 2> $OUT/trace_$name.err
   echo "trace $name rc=$?"
 }
 trace ur_high_5 --steps 104 --warmup 20 --age-steps 0
@@ -29,6 +29,6 @@ pmc cam_write WRITE_SIZE -- --workload from_the_readme --steps 16 --warmup 30
 pmc cam_fetch FETCH_SIZE -- --workload from_the_readme --steps 16 --warmup 30
 pmc cam_sq SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY -- --workload from_the_readme --steps 16 --warmup 30
 # the bench line with its own counter passes (traffic / VALU share measured in the same invocation)
-python3 bench.py > $OUT/bench_ur_high_5_default.json 2> $OUT/bench_default.err; echo "default bench rc=$?"
-python3 bench.py --workload from_the_readme --steps 40 --warmup 30 --age-steps 0 --no-api > $OUT/bench_from_the_readme_default.json 2> $OUT/bench_readme_default.err; echo "readme bench rc=$?"
+python3 bench.py --full > $OUT/bench_ur_high_5_default.json 2> $OUT/bench_default.err; echo "default bench rc=$?"
+python3 bench.py --full --workload from_the_readme --steps 40 --warmup 30 --age-steps 0 --no-api > $OUT/bench_from_the_readme_default.json 2> $OUT/bench_readme_default.err; echo "readme bench rc=$?"
 find $OUT -name "*kernel_stats.csv" -o -name "*counter_collection.csv" | head -40
