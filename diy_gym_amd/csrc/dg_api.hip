@@ -22,6 +22,19 @@ namespace dg {
 extern const LaunchTable g_launch_table_64, g_launch_table_32, g_launch_table_16, g_launch_table_8, g_launch_table_4, g_launch_table_1, g_launch_table_0, g_launch_table_g16;
 const LaunchTable& launch_table(int lanes) { return lanes == 64 ? g_launch_table_64 : lanes == 32 ? g_launch_table_32 : lanes == 16 ? g_launch_table_16 : lanes == 8 ? g_launch_table_8 : lanes == 4 ? g_launch_table_4 : lanes == 1 ? g_launch_table_1 : lanes == -16 ? g_launch_table_g16 : g_launch_table_0; }
 }  // namespace dg
+// the same kernels with the hull-hull contact manifold compiled in (dg_inst.hip -DDG_MANIFOLD: the headers in namespace dg_mf, the
+// same types member for member); no helper-wave form
+namespace dg_mf {
+extern const dg::LaunchTable g_launch_table_64, g_launch_table_32, g_launch_table_16, g_launch_table_8, g_launch_table_4, g_launch_table_1, g_launch_table_0, g_launch_table_g16;
+}
+namespace dg {
+const LaunchTable& launch_table(int lanes, bool mf) {
+  namespace m = dg_mf;
+  if (!mf) return launch_table(lanes);
+  return lanes == 64 ? m::g_launch_table_64 : lanes == 32 ? m::g_launch_table_32 : lanes == 16 ? m::g_launch_table_16 : lanes == 8 ? m::g_launch_table_8 :
+         lanes == 4 ? m::g_launch_table_4 : lanes == 1 ? m::g_launch_table_1 : lanes == -16 ? m::g_launch_table_g16 : m::g_launch_table_0;
+}
+}  // namespace dg
 
 static thread_local std::string g_err;
 static int fail(int code, const char* fmt, ...) {
@@ -56,6 +69,7 @@ struct dg_world {
   int32_t* diag = nullptr;
   unsigned long long* profile_cycles = nullptr;
   bool par = false;  // step runs as two wavefronts per workgroup (helper wave)
+  bool mf = false;   // hull_manifold_points > 1 in a world that collides two hulls: the kernels with the manifold (dg_mf)
   bool no_par_reset = false;  // DG_NO_PAR_RESET: masked resets through reset_kernel<64> (one wavefront, generic solver)
   float* d_gws = nullptr;  // global scratch when the scene does not fit LDS (lanes == 0)
   float* d_hull_ws = nullptr;  // polytope workspace of the hull-hull narrow phase (dg_hull.h), one block per wavefront of the step grid
@@ -320,7 +334,11 @@ int32_t dg_world_create(const int32_t* I, int64_t n_i, const double* F, int64_t 
   // helper wave: the LAST fixed-base chain body (so that wave 0 keeps the first arm), provided the scene has other
   // work to overlap with and every inverse-kinematics op on that body has the register-resident form
   sc.helper_body = -1;
-  if (lanes == 64 && ncons == 0 && !getenv("DG_NO_HELPER_WAVE")) {
+  { bool hull_pairs = false; const int32_t* PIh = I + I[DG_H_OFF_PAIR_I]; const int32_t* SIh = I + I[DG_H_OFF_SHAPE_I];
+    for (int p = 0; p < I[DG_H_N_PAIRS] && !hull_pairs; p++)
+      hull_pairs = SIh[PIh[p * DG_PI_STRIDE + DG_PI_A] * DG_SI_STRIDE + DG_SI_TYPE] == DG_SHAPE_POINTS && SIh[PIh[p * DG_PI_STRIDE + DG_PI_B] * DG_SI_STRIDE + DG_SI_TYPE] == DG_SHAPE_POINTS;
+    w->mf = hull_pairs && F[DG_HF_HULL_CONTACTS] > 0 && F[DG_HF_HULL_MANIFOLD] > 1; }
+  if (lanes == 64 && ncons == 0 && !w->mf && !getenv("DG_NO_HELPER_WAVE")) {  // (the manifold has no helper-wave form)
     int n_dyn = 0; for (int b = 0; b < nb; b++) { const int32_t* B = BI + b * DG_BI_STRIDE; if (!((B[DG_BI_FLAGS] & DG_BODY_FIXED) && B[DG_BI_N_LINKS] == 0)) n_dyn++; }
     for (int b = nb - 1; b >= 0 && n_dyn >= 2; b--) {
       if (!PLB[b * PLB_STRIDE + PLB_CHAIN]) continue;
@@ -418,7 +436,7 @@ int32_t dg_world_create(const int32_t* I, int64_t n_i, const double* F, int64_t 
   w->ncam = I[DG_H_N_CAMERAS]; w->d_CI = dI + I[DG_H_OFF_CAMERA_I]; w->d_CF = dF + I[DG_H_OFF_CAMERA_F]; w->d_PLN = dF + I[DG_H_OFF_PLANE_F];
   if (w->ncam > 0) HIP_TRY(hipMalloc((void**)&w->d_render_table, sizeof(float) * (size_t)num_envs * (size_t)(sc.nsh * RS_STRIDE + w->ncam * RC_STRIDE)));
   // allow > 64 KiB of dynamic LDS for this mode's kernels
-  HIP_TRY(launch_table(lanes).prepare(w->lds_bytes));
+  HIP_TRY(launch_table(lanes, w->mf).prepare(w->lds_bytes));
   *out = holder.release();
   return DG_OK;
 }
@@ -467,9 +485,9 @@ int32_t dg_world_reset(dg_world* w, float* state, const uint8_t* mask, float* ob
   // four-wavefront scenes with the usual single hot-start step: the reset ops and that step run in the step kernel itself
   // (reset mode), the envs the mask does not name computing in their scratch workspace with stores off
   if (w->par && w->sc.hot_start == 1 && !w->no_par_reset)
-    launch_table(w->lanes).step_par(grid_of(w), w->lds_bytes, (hipStream_t)stream, false, w->sc, w->mt, state, nullptr, 0ull, obs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mask, 1);
+    launch_table(w->lanes, w->mf).step_par(grid_of(w), w->lds_bytes, (hipStream_t)stream, false, w->sc, w->mt, state, nullptr, 0ull, obs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mask, 1);
   else
-    launch_table(w->lanes).reset(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, mask, obs, w->d_gws);
+    launch_table(w->lanes, w->mf).reset(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, mask, obs, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }
@@ -497,7 +515,7 @@ int32_t dg_world_step(dg_world* w, float* state, const float* actions, uint64_t 
     }
   }
   {
-    const LaunchTable& lt = launch_table(w->lanes); const bool prof = w->profile_cycles != nullptr;
+    const LaunchTable& lt = launch_table(w->lanes, w->mf); const bool prof = w->profile_cycles != nullptr;
     if (prof && !lt.has_prof) return fail(DG_ERR_UNSUPPORTED, "in-kernel stamps are not built for this workspace mode");
     if (w->par) lt.step_par(grid_of(w), w->lds_bytes, (hipStream_t)stream, prof, w->sc, w->mt, state, actions, update_mask, obs, rew, term, rew_sum, term_flag, w->diag, w->profile_cycles, nullptr, 0);
     else lt.step(grid_of(w), w->lds_bytes, (hipStream_t)stream, prof, w->sc, w->mt, state, actions, update_mask, obs, rew, term, rew_sum, term_flag, w->diag, w->profile_cycles, w->d_gws);
@@ -510,7 +528,7 @@ int32_t dg_world_render(dg_world* w, const float* state, int32_t camera, float* 
   if (!w || !state) return fail(DG_ERR_ARG, "null argument");
   if (camera < 0 || camera >= w->ncam) return fail(DG_ERR_ARG, "camera %d out of range (scene has %d)", camera, w->ncam);
   DG_ON_DEVICE(w->device);
-  launch_table(w->lanes).pose(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), w->ncam, w->d_CI, w->d_CF, w->d_render_table, w->d_gws);
+  launch_table(w->lanes, w->mf).pose(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), w->ncam, w->d_CI, w->d_CF, w->d_render_table, w->d_gws);
   HIP_TRY(hipGetLastError());
   const int32_t* I = w->I.data(); const int32_t* ci = I + I[DG_H_OFF_CAMERA_I] + camera * DG_CI_STRIDE;
   // Rows per workgroup: a multiple of 8 (the tile height of render_kernel's wavefronts; 200-wide images: whole cache lines).
@@ -584,12 +602,67 @@ int32_t dg_debug_hull_hull(const float* pts_a, int32_t na, const float* pts_b, i
   return DG_OK;
 }
 
+// diagnostics: the contacts the narrow phase makes of one hull pair with DG_HF_HULL_MANIFOLD = npts (dg_hull.h hull_manifold after
+// hull_hull, as dg_solver.h collide calls them), one pair of poses per lane -- tests/test_hull_manifold.py compares it with its numpy
+// restatement; host pointers; not part of the public header.  poses [n][24] as dg_debug_hull_hull; rad_a, rad_b: the hulls' bounding
+// radii (the feature tolerance scales with them).  out [n][25] = contacts (0..npts), 1 if that is the pair's single contact (no
+// manifold), normal from B towards A (3), then per slot s < 4: point (3, world), depth (distance - 2 x hull_margin), key feature,
+// unused slots zero.
+__global__ __launch_bounds__(64) void hull_manifold_kernel(cfp pts, int na, int nb, float rad_a, float rad_b, const float* poses, int n, float margin,
+                                                            float hmg, int npts, float* out, float* ws) {
+  const int i = blockIdx.x * 64 + threadIdx.x; const bool have = i < n; const float* p = poses + 24 * (size_t)(have ? i : n - 1);
+  HullPairD h; h.pa = pts; h.na = na; h.pb = pts + 3 * na; h.nb = nb;
+#pragma unroll
+  for (int k = 0; k < 9; k++) { h.RA.m[k] = p[k]; h.RB.m[k] = p[12 + k]; }
+  const V3 ta = v3(p[9], p[10], p[11]), tb = v3(p[21], p[22], p[23]); h.tBA = tb - ta;
+  V3 ca = v3(0.f, 0.f, 0.f), cb = ca;  // (seed as dg_debug_hull_hull)
+  for (int k = 0; k < na; k++) ca = ca + v3(h.pa[3 * k], h.pa[3 * k + 1], h.pa[3 * k + 2]);
+  for (int k = 0; k < nb; k++) cb = cb + v3(h.pb[3 * k], h.pb[3 * k + 1], h.pb[3 * k + 2]);
+  const V3 seed = mul(h.RA, ca * (1.0f / (float)na)) - (mul(h.RB, cb * (1.0f / (float)nb)) + h.tBA);
+  h.ew = hull_ws_of(ws); hull_tables(h, na <= 64 && nb <= 64);
+  HullHit hh; hull_hull(h, seed, margin + 2.f * hmg, have, hh);
+  const bool hit = hh.hit && hh.dist - 2.f * hmg < margin;
+  const int m = npts > 1 ? hull_manifold(h, hh.n, rad_a, rad_b, margin, hmg, npts, hit) : 0;
+  if (!have) return;
+  float* o = out + 25 * (size_t)i;
+  for (int k = 0; k < 25; k++) o[k] = 0.f;
+  if (!hit) return;
+  o[0] = (float)(m > 0 ? m : 1); o[1] = m > 0 ? 0.f : 1.f; o[2] = hh.n.x; o[3] = hh.n.y; o[4] = hh.n.z;
+  if (m == 0) {
+    const V3 pa = (hh.pa + ta) - hh.n * hmg, pb = (hh.pb + ta) + hh.n * hmg, c = (pa + pb) * 0.5f;
+    o[5] = c.x; o[6] = c.y; o[7] = c.z; o[8] = hh.dist - 2.f * hmg; o[9] = 0.f;
+  } else {
+    const HEpa E = {h.ew};
+    for (int s = 0; s < m; s++) {
+      o[5 + 5 * s] = E.F(MF_R + 4 * s) + ta.x; o[6 + 5 * s] = E.F(MF_R + 4 * s + 1) + ta.y; o[7 + 5 * s] = E.F(MF_R + 4 * s + 2) + ta.z;
+      o[8 + 5 * s] = E.F(MF_R + 4 * s + 3); o[9 + 5 * s] = (float)s;
+    }
+  }
+}
+int32_t dg_debug_hull_manifold(const float* pts_a, int32_t na, const float* pts_b, int32_t nb, float rad_a, float rad_b, const float* poses, int32_t n,
+                               float margin, float hull_margin, int32_t npts, float* out25 /* [n][25] */) {
+  if (!pts_a || !pts_b || !poses || !out25 || na < 1 || nb < 1 || na > 256 || nb > 256 || n < 1 || npts < 1 || npts > 4)
+    return fail(DG_ERR_ARG, "dg_debug_hull_manifold: bad argument");
+  struct Bufs { float *pts = nullptr, *poses = nullptr, *out = nullptr, *ws = nullptr;
+                ~Bufs() { (void)hipFree(pts); (void)hipFree(poses); (void)hipFree(out); (void)hipFree(ws); } } b;  // (freed on every way out)
+  const size_t blocks = (size_t)((n + 63) / 64);
+  HIP_TRY(hipMalloc(&b.ws, sizeof(float) * blocks * (size_t)HH_WS_SLOTS * 64));
+  HIP_TRY(hipMalloc(&b.pts, sizeof(float) * 3 * (size_t)(na + nb))); HIP_TRY(hipMalloc(&b.poses, sizeof(float) * 24 * (size_t)n)); HIP_TRY(hipMalloc(&b.out, sizeof(float) * 25 * (size_t)n));
+  HIP_TRY(hipMemcpy(b.pts, pts_a, sizeof(float) * 3 * (size_t)na, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(b.pts + 3 * na, pts_b, sizeof(float) * 3 * (size_t)nb, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b.poses, poses, sizeof(float) * 24 * (size_t)n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(hull_manifold_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)0, (cfp)b.pts, na, nb, rad_a, rad_b, (const float*)b.poses, n,
+                     margin, hull_margin, (int)npts, b.out, b.ws);
+  HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out25, b.out, sizeof(float) * 25 * (size_t)n, hipMemcpyDeviceToHost));
+  return DG_OK;
+}
+
 int32_t dg_world_set_profile_buffer(dg_world* w, uint64_t* cycles) { if (!w) return fail(DG_ERR_ARG, "null world"); w->profile_cycles = (unsigned long long*)cycles; return DG_OK; }
 
 int32_t dg_world_observe(dg_world* w, const float* state, float* obs, float* rew, uint8_t* term, float* rew_sum, uint8_t* term_flag, void* stream) {
   if (!w || !state) return fail(DG_ERR_ARG, "null argument");
   DG_ON_DEVICE(w->device);
-  launch_table(w->lanes).observe(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), obs, rew, term, rew_sum, term_flag, w->d_gws);
+  launch_table(w->lanes, w->mf).observe(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), obs, rew, term, rew_sum, term_flag, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }
@@ -605,7 +678,7 @@ int32_t dg_world_frame_state(dg_world* w, const float* state, int32_t body, int3
     if (!found) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
   }
   DG_ON_DEVICE(w->device);
-  launch_table(w->lanes).frame(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, gf, com, out, w->d_gws);
+  launch_table(w->lanes, w->mf).frame(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, gf, com, out, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }
@@ -631,7 +704,7 @@ int32_t dg_world_apply_wrench(dg_world* w, float* state, int32_t body, int32_t f
   }
   if (!force && !torque) return DG_OK;
   DG_ON_DEVICE(w->device);
-  launch_table(w->lanes).wrench(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, gf, flags == DG_WRENCH_LINK_FRAME ? 1 : 0, force, pos, torque, w->d_gws);
+  launch_table(w->lanes, w->mf).wrench(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, gf, flags == DG_WRENCH_LINK_FRAME ? 1 : 0, force, pos, torque, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }

@@ -305,4 +305,166 @@ HH_FN void hull_hull(const HullPairD& h, V3 seed, float max_dist, bool active, H
   }
 }
 
+// ---- one-shot contact manifold (DG_HF_HULL_MANIFOLD > 1): up to four points of a hull pair, rebuilt every substep from the pair's
+// normal n (B towards A).  Restated in numpy by tests/manifold_ref.py -- same steps, constants and tie-breaks.
+//   1. feature of A: its points within tol = DG_HULL_MANIFOLD_TOL x bounding radius of its extreme along -n; of B: along n.  At
+//      most HH_MF_CAP points each: the extreme point, then the lowest point indices.  (On a curved hull the angle order can make
+//      C non-convex; clipping against its edges then keeps a subset of C's convex hull -- never a point outside C.)  Each ordered by angle about its centroid in the plane normal
+//      to n (basis u, v = n x u: u is A's link-frame x axis -- y when x is within 26 degrees of n -- projected on the plane):
+//      counter-clockwise about n.
+//   2. a single point on either side, or two crossed edges: no manifold (the caller keeps the pair's one contact).  Otherwise the
+//      reference feature C is A if it has >= 3 points, else B if it has, else A's edge (parallel edges); the other, S, is clipped
+//      against the half-planes of C's edges (a polygon: Sutherland-Hodgman, <= HH_MF_CLIP vertices; an edge: its parameter
+//      interval).  A clipped point x of S is separated along n from C's feature plane (its own normal: a tilted face is
+//      measured as tilted, whichever hull is A) by sep: depth = sep - 2 x hull margin, kept if below the contact margin; the
+//      contact point is the midpoint between x and that plane along n.
+//   3. reduction to N: the deepest point, the one farthest from it, the one that spans the largest triangle with those two, the one
+//      that adds the most area outside that triangle (Bullet's sortCachedPoints idea); strict comparisons, lowest index first.
+//   4. slots: the chosen points ordered by angle about their centroid, from u: slot s gets key DG_CONTACT_KEY(pair, s).
+// Everything per lane lives in the lane's column of the polytope workspace (dead once hh_epa has returned), never in private
+// arrays with run-time indices.  The point loops are wave-uniform (lane tables / scalar loads, as the support loop); the rest runs
+// under divergence on memory only.
+#define HH_MF_CAP 8
+#define HH_MF_CLIP 16
+enum { MF_A = 0 /* A's feature, ordered: 3 x CAP */, MF_B = 3 * HH_MF_CAP, MF_T = 6 * HH_MF_CAP /* unordered points 3 x CAP, angles CAP */,
+       MF_P0 = 10 * HH_MF_CAP /* clip buffers: 3 x CLIP each */, MF_P1 = MF_P0 + 3 * HH_MF_CLIP, MF_D = MF_P1 + 3 * HH_MF_CLIP /* depths */,
+       MF_R = MF_D + HH_MF_CLIP /* result: 4 x (midpoint 3, depth) in slot order */, MF_END = MF_R + 16 };
+static_assert(MF_END <= HH_WS_SLOTS, "manifold buffers must fit the polytope workspace");
+// angle about the origin as a monotone stand-in in [0, 4) (0 along +x, counter-clockwise)
+DGD float hh_pseudo_angle(float x, float y) {
+  const float s = fabsf(x) + fabsf(y); if (!(s > 0.f)) return 0.f;
+  const float p = y / s; return x < 0.f ? 2.f - p : (y < 0.f ? 4.f + p : p);
+}
+template <int SIDE> DGD V3 hh_point(const HullPairD& h, int k) {  // point k of A (0) / B (1) in its link frame; k wave-uniform
+  auto rl = [](float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); };
+  if (h.tabled) return SIDE ? v3(rl(h.tbx, k), rl(h.tby, k), rl(h.tbz, k)) : v3(rl(h.tax, k), rl(h.tay, k), rl(h.taz, k));
+  const hh_cfp p = SIDE ? h.pb : h.pa; return v3(p[3 * k], p[3 * k + 1], p[3 * k + 2]);
+}
+// feature of one side into `dst` (ordered), its point count; *href = its extreme along n (A: lowest, B: highest)
+template <int SIDE>
+HH_FN int hh_feature(const HullPairD& h, const HEpa& E, V3 n, V3 u, V3 v, float tol, bool active, int dst, float& href) {
+  const M3& R = SIDE ? h.RB : h.RA; const int np = SIDE ? h.nb : h.na;
+  const V3 dl = tmul(R, SIDE ? n : -n);
+  float s = -3.0e38f; int ks = 0;
+  for (int k = 0; k < np; k++) { const float d = dot(hh_point<SIDE>(h, k), dl); if (d > s) { s = d; ks = k; } }
+  int m = 0; V3 c = v3(0.f, 0.f, 0.f);
+  for (int k = 0; k < np; k++) {  // (the extreme point ks always; the others by index, a slot kept free for ks until it comes)
+    const V3 p = hh_point<SIDE>(h, k);
+    if (active && (k == ks || m < HH_MF_CAP - (k < ks ? 1 : 0)) && dot(p, dl) >= s - tol) {
+      const V3 x = SIDE ? mul(R, p) + h.tBA : mul(R, p);
+      E.F(MF_T + 3 * m) = x.x; E.F(MF_T + 3 * m + 1) = x.y; E.F(MF_T + 3 * m + 2) = x.z; c = c + x; m++;
+    }
+  }
+  href = SIDE ? s + dot(h.tBA, n) : -s;
+  if (!active || m == 0) return 0;
+  c = c * (1.f / (float)m);
+  for (int i = 0; i < m; i++) { const V3 d = v3(E.F(MF_T + 3 * i), E.F(MF_T + 3 * i + 1), E.F(MF_T + 3 * i + 2)) - c; E.F(MF_T + 3 * HH_MF_CAP + i) = hh_pseudo_angle(dot(d, u), dot(d, v)); }
+  for (int i = 0; i < m; i++) {
+    const float ai = E.F(MF_T + 3 * HH_MF_CAP + i); int r = 0;
+    for (int j = 0; j < m; j++) { const float aj = E.F(MF_T + 3 * HH_MF_CAP + j); r += (aj < ai || (aj == ai && j < i)) ? 1 : 0; }
+    E.F(dst + 3 * r) = E.F(MF_T + 3 * i); E.F(dst + 3 * r + 1) = E.F(MF_T + 3 * i + 1); E.F(dst + 3 * r + 2) = E.F(MF_T + 3 * i + 2);
+  }
+  return m;
+}
+// number of manifold points written to MF_R (slot order), 0: keep the pair's single contact.  Coordinates relative to A's origin.
+HH_FN int hull_manifold(const HullPairD& h, V3 n, float rad_a, float rad_b, float margin, float hmg, int npts, bool active) {
+  const HEpa E = {h.ew};
+  V3 a = v3(h.RA.m[0], h.RA.m[3], h.RA.m[6]);
+  if (fabsf(dot(a, n)) > 0.9f) a = v3(h.RA.m[1], h.RA.m[4], h.RA.m[7]);
+  V3 u = a - n * dot(a, n); u = u * frsq(dot(u, u)); const V3 v = cross(n, u);
+  float hA, hB;
+  const int ma = hh_feature<0>(h, E, n, u, v, DG_HULL_MANIFOLD_TOL * rad_a, active, MF_A, hA);
+  const int mb = hh_feature<1>(h, E, n, u, v, DG_HULL_MANIFOLD_TOL * rad_b, active, MF_B, hB);
+  if (!active || ma < 2 || mb < 2) return 0;
+  auto X = [&](int base, int i) { return v3(E.F(base + 3 * i), E.F(base + 3 * i + 1), E.F(base + 3 * i + 2)); };
+  auto put = [&](int base, int i, V3 x) { E.F(base + 3 * i) = x.x; E.F(base + 3 * i + 1) = x.y; E.F(base + 3 * i + 2) = x.z; };
+  if (ma == 2 && mb == 2) {  // two edges: crossed (no manifold) or parallel
+    const V3 ea = X(MF_A, 1) - X(MF_A, 0), eb = X(MF_B, 1) - X(MF_B, 0), cx = cross(ea, eb);
+    if (dot(cx, cx) > DG_HULL_MANIFOLD_TOL * DG_HULL_MANIFOLD_TOL * dot(ea, ea) * dot(eb, eb)) return 0;
+  }
+  const bool refA = ma >= 3 || mb < 3;  // the reference feature C: A, unless only B is a polygon
+  const int cb = refA ? MF_A : MF_B, mc = refA ? ma : mb, sb = refA ? MF_B : MF_A, ms = refA ? mb : ma;
+  const float href = refA ? hA : hB, sgn = refA ? -1.f : 1.f;
+  const int npl = mc >= 3 ? mc : 2;
+  auto plane = [&](int j, V3& q, V3& d) {  // half-plane j of C: dot(x - q, d) >= 0 inside
+    if (mc >= 3) { q = X(cb, j); d = cross(n, X(cb, j + 1 < mc ? j + 1 : 0) - q); }
+    else { q = X(cb, j); d = X(cb, 1 - j) - q; }
+  };
+  int src, cnt;
+  if (ms == 2) {  // an edge: its parameter interval inside every half-plane
+    const V3 p0 = X(sb, 0), dir = X(sb, 1) - p0; float t0 = 0.f, t1 = 1.f;
+    for (int j = 0; j < npl; j++) {
+      V3 q, d; plane(j, q, d); const float f0 = dot(p0 - q, d), fd = dot(dir, d);
+      if (fd == 0.f) { if (f0 < 0.f) t1 = -1.f; }
+      else if (fd > 0.f) t0 = fmaxf(t0, -f0 / fd);
+      else t1 = fminf(t1, -f0 / fd);
+    }
+    cnt = 0; src = MF_P0;
+    if (t0 <= t1) { put(MF_P0, 0, p0 + dir * t0); put(MF_P0, 1, p0 + dir * t1); cnt = 2; }
+  } else {  // a polygon: Sutherland-Hodgman, ping-pong between the two clip buffers
+    src = sb; cnt = ms; int dst = MF_P0;
+    for (int j = 0; j < npl && cnt > 0; j++) {
+      V3 q, d; plane(j, q, d); int oc = 0;
+      V3 prev = X(src, cnt - 1); float fp = dot(prev - q, d);
+      for (int i = 0; i < cnt; i++) {
+        const V3 cur = X(src, i); const float fc = dot(cur - q, d);
+        if ((fc >= 0.f) != (fp >= 0.f) && oc < HH_MF_CLIP) { put(dst, oc, prev + (cur - prev) * (fp / (fp - fc))); oc++; }
+        if (fc >= 0.f && oc < HH_MF_CLIP) { put(dst, oc, cur); oc++; }
+        prev = cur; fp = fc;
+      }
+      cnt = oc; src = dst; dst = dst == MF_P0 ? MF_P1 : MF_P0;
+    }
+  }
+  // C's feature plane: through its centroid, normal = the polygon's area vector (Newell); an edge: the plane through it nearest to
+  // normal to n.  A feature whose plane leans more than ~26 degrees from n (nearly collinear points) falls back to the plane
+  // normal to n through C's extreme
+  V3 c0 = v3(0.f, 0.f, 0.f), nc = v3(0.f, 0.f, 0.f);
+  for (int j = 0; j < mc; j++) c0 = c0 + X(cb, j);
+  c0 = c0 * (1.f / (float)mc);
+  if (mc >= 3) { for (int j = 0; j < mc; j++) nc = nc + cross(X(cb, j) - c0, X(cb, j + 1 < mc ? j + 1 : 0) - c0); }
+  else { const V3 e = X(cb, 1) - X(cb, 0); const float ee = dot(e, e); nc = ee > 1e-20f ? n - e * (dot(e, n) / ee) : n; }
+  float dn = dot(n, nc);
+  if (!(dn * dn >= 0.81f * dot(nc, nc)) || !(dn != 0.f)) { nc = n; c0 = n * href; dn = 1.f; }
+  // depths: along n from a clipped point x of S to C's plane (x + t n on it); the points below the contact margin, as midpoints,
+  // into the other clip buffer
+  const int kb = src == MF_P0 ? MF_P1 : MF_P0; int nk = 0;
+  for (int i = 0; i < cnt; i++) {
+    const V3 x = X(src, i); const float t = -dot(x - c0, nc) / dn, sep = -sgn * t, depth = sep - 2.f * hmg;
+    if (depth < margin) { put(kb, nk, x + n * (0.5f * t)); E.F(MF_D + nk) = depth; nk++; }
+  }
+  if (nk == 0) return 0;
+  // reduction: deepest, farthest from it, largest triangle, most area added outside the triangle
+  int i0 = 0; { float bd = E.F(MF_D); for (int i = 1; i < nk; i++) { const float di = E.F(MF_D + i); if (di < bd) { bd = di; i0 = i; } } }
+  const V3 x0 = X(kb, i0); int i1 = -1, i2 = -1, i3 = -1;
+  if (npts >= 2) { float bs = -3.0e38f; for (int i = 0; i < nk; i++) { const V3 e = X(kb, i) - x0; const float s = dot(e, e); if (i != i0 && s > bs) { bs = s; i1 = i; } } }
+  const V3 x1 = X(kb, i1 < 0 ? i0 : i1);
+  if (npts >= 3 && i1 >= 0) { float bs = -3.0e38f; for (int i = 0; i < nk; i++) { const V3 c = cross(x1 - x0, X(kb, i) - x0); const float s = dot(c, c); if (i != i0 && i != i1 && s > bs) { bs = s; i2 = i; } } }
+  const V3 x2 = X(kb, i2 < 0 ? i0 : i2);
+  if (npts >= 4 && i2 >= 0) {
+    const float o = dot(cross(x1 - x0, x2 - x0), n) >= 0.f ? -1.f : 1.f;  // (outside of a counter-clockwise edge: negative)
+    float bs = -3.0e38f;
+    for (int i = 0; i < nk; i++) {
+      const V3 x = X(kb, i);
+      const float s = fmaxf(fmaxf(o * dot(cross(x1 - x0, x - x0), n), o * dot(cross(x2 - x1, x - x1), n)), o * dot(cross(x0 - x2, x - x2), n));
+      if (i != i0 && i != i1 && i != i2 && s > bs) { bs = s; i3 = i; }
+    }
+  }
+  const int m = 1 + (i1 >= 0) + (i2 >= 0) + (i3 >= 0);
+  const V3 x3 = X(kb, i3 < 0 ? i0 : i3);
+  const V3 cm = (((x0 + (i1 >= 0 ? x1 : v3(0.f, 0.f, 0.f))) + (i2 >= 0 ? x2 : v3(0.f, 0.f, 0.f))) + (i3 >= 0 ? x3 : v3(0.f, 0.f, 0.f))) * (1.f / (float)m);
+  const float g0 = hh_pseudo_angle(dot(x0 - cm, u), dot(x0 - cm, v)), g1 = hh_pseudo_angle(dot(x1 - cm, u), dot(x1 - cm, v));
+  const float g2 = hh_pseudo_angle(dot(x2 - cm, u), dot(x2 - cm, v)), g3 = hh_pseudo_angle(dot(x3 - cm, u), dot(x3 - cm, v));
+  // slot of choice c: the chosen points before it by angle (ties: earlier choice first)
+  const int r0 = (m > 1 && g1 < g0) + (m > 2 && g2 < g0) + (m > 3 && g3 < g0);
+  const int r1 = (g0 <= g1) + (m > 2 && g2 < g1) + (m > 3 && g3 < g1);
+  const int r2 = (g0 <= g2) + (g1 <= g2) + (m > 3 && g3 < g2);
+  const int r3 = (g0 <= g3) + (g1 <= g3) + (g2 <= g3);
+  auto res = [&](int slot, int i, V3 x) { E.F(MF_R + 4 * slot) = x.x; E.F(MF_R + 4 * slot + 1) = x.y; E.F(MF_R + 4 * slot + 2) = x.z; E.F(MF_R + 4 * slot + 3) = E.F(MF_D + i); };
+  res(r0, i0, x0);
+  if (m > 1) res(r1, i1, x1);
+  if (m > 2) res(r2, i2, x2);
+  if (m > 3) res(r3, i3, x3);
+  return m;
+}
+
 }  // namespace dg

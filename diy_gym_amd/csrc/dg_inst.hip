@@ -3,7 +3,12 @@
 //                            -DDG_PART=1  reset / observe / frame / pose kernels and the mode's launch table
 //   -DDG_LANES=64            -DDG_PART=2  helper-wave step kernels
 //   -DDG_LANES=-16 -DDG_TAG=g16           the global-workspace mode with 16 envs per wavefront
+//   -DDG_MANIFOLD (with any of the above but the helper-wave part): the same kernels with the hull-hull contact manifold compiled
+//                 in (hull_manifold_points > 1), in namespace dg_mf so that they do not clash with the default ones
 #include <hip/hip_runtime.h>
+#ifdef DG_MANIFOLD
+#define dg dg_mf
+#endif
 #include "dg_launch.h"
 #include "dg_entry.h"
 
@@ -21,7 +26,7 @@ constexpr bool HAS_PROF = (DG_LANES == 64 || DG_LANES == 32 || DG_LANES == 16 ||
 
 void DGL(l_step)(dim3 grid, int lds, hipStream_t st, bool prof, DG_STEP_PARAMS, float* gws);
 hipError_t DGL(l_prepare_step)(int lds);
-#if DG_LANES == 64
+#if DG_LANES == 64 && !defined(DG_MANIFOLD)
 void l_step_par_64(dim3 grid, int lds, hipStream_t st, bool prof, DG_STEP_PARAMS, const uint8_t* reset_mask, int reset_mode);
 hipError_t l_prepare_par_64(int lds);
 #endif
@@ -73,7 +78,7 @@ static hipError_t l_prepare(int lds) {
 #define DG_ATTR(K) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
   DG_ATTR(reset_kernel<L>); DG_ATTR(observe_kernel<L>); DG_ATTR(frame_kernel<L>); DG_ATTR(wrench_kernel<L>); DG_ATTR(pose_kernel<L>);
 #undef DG_ATTR
-#if DG_LANES == 64
+#if DG_LANES == 64 && !defined(DG_MANIFOLD)
   if (e == hipSuccess) e = l_prepare_par_64(lds);
 #endif
   return e;
@@ -81,7 +86,7 @@ static hipError_t l_prepare(int lds) {
 #ifndef __HIP_DEVICE_COMPILE__  // a host-side table of host function pointers
 extern const LaunchTable DGL(g_launch_table) = {
     HAS_PROF, l_prepare, DGL(l_step),
-#if DG_LANES == 64
+#if DG_LANES == 64 && !defined(DG_MANIFOLD)
     l_step_par_64,
 #else
     nullptr,

@@ -284,7 +284,26 @@ DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff
       HullHit hh; hull_hull(hp, dc, margin + 2.f * hmg, close, hh);
       Hit h; h.hit = hh.hit && hh.dist - 2.f * hmg < margin; h.n = hh.n; h.dist = hh.dist - 2.f * hmg;
       h.pa = (hh.pa + pla) - hh.n * hmg; h.pb = (hh.pb + pla) + hh.n * hmg;
+      // DG_HF_HULL_MANIFOLD > 1: up to that many points along the same normal (dg_hull.h hull_manifold); a lane without a manifold
+      // (a vertex or crossed edges) keeps the one contact
+      // -- compiled only into the kernels of worlds with hull_manifold_points > 1 (DG_MANIFOLD, dg_inst.hip): the code raises the
+      // register pressure of every kernel it is in, and the one-point default keeps its kernels exactly as they were
+#ifndef DG_MANIFOLD
       emit_contact(ln, list, cnt, pi, h, flip);
+#else
+      int mcnt = 0; const int mfn = (int)sc.HF[DG_HF_HULL_MANIFOLD];
+      if (mfn > 1 && __any(h.hit)) mcnt = hull_manifold(hp, hh.n, ln.L(oa + SC_BOUND), ln.L(ob + SC_BOUND), margin, hmg, mfn, h.hit);
+      if (mcnt == 0) emit_contact(ln, list, cnt, pi, h, flip);
+      else {
+        const HEpa E = {hp.ew};
+        hh_for<0, 4>([&](auto S) {
+          constexpr int s = decltype(S)::value;
+          Hit hs; hs.hit = s < mcnt; hs.n = hh.n; hs.dist = E.F(MF_R + 4 * s + 3);
+          hs.pa = v3(E.F(MF_R + 4 * s), E.F(MF_R + 4 * s + 1), E.F(MF_R + 4 * s + 2)) + pla; hs.pb = hs.pa;
+          emit_contact(ln, list, cnt, pi, hs, flip, s);
+        });
+      }
+#endif
     } else
 #endif
     if (tb != DG_SHAPE_BOX) {

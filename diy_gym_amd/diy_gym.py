@@ -43,7 +43,7 @@ class DIYGym(Receptor):
     metadata = {'render.modes': []}
 
     def __init__(self, config_file, num_envs=None, device=None, seed=0, env_index_base=0, backend_factory=None,
-                 max_hull_points=32, engine=None):
+                 max_hull_points=32, engine=None, hull_manifold_points=1):
         Receptor.__init__(self)
         config = config_file if isinstance(config_file, Configuration) else Configuration.from_file(config_file)
         self.env = self
@@ -54,6 +54,9 @@ class DIYGym(Receptor):
         if not 4 <= int(max_hull_points) <= 256:
             raise ValueError('max_hull_points must be in [4, 256] (a contact is identified by its hull vertex, DG_CONTACT_KEY)')
         self.max_hull_points = max_hull_points
+        if engine and 'hull_manifold_points' in engine:  # (a keyword of its own: the checker does not implement it)
+            raise KeyError('unknown engine parameter: hull_manifold_points (pass DIYGym(..., hull_manifold_points=N))')
+        self.hull_manifold_points = hull_manifold_points
         self._max_episode_steps = config.get('max_episode_steps') if 'max_episode_steps' in config else None
         self.hot_start = config.get('hot_start', 1)
 
@@ -74,7 +77,8 @@ class DIYGym(Receptor):
         self.builder = SceneBuilder(timestep=timestep, substeps=sub_steps, solver_iterations=iterations, gravity=gravity,
                                     max_episode_steps=self._max_episode_steps, hot_start=self.hot_start,
                                     rew_mode=K.COLLAPSE_SUM if self.collapse_rewards_func else K.COLLAPSE_NONE,
-                                    term_mode=term_mode, max_contacts=config.get('max_contacts', None), **(engine or {}))
+                                    term_mode=term_mode, max_contacts=config.get('max_contacts', None),
+                                    hull_manifold_points=hull_manifold_points, **(engine or {}))
 
         # models in YAML order (body ids follow it), stored sorted by name (diy_gym.py:84-86)
         built = [(child.name, Model(child, env=self)) for child in config.find_all('model')]

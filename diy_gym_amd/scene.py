@@ -24,7 +24,8 @@ def _parse_header(path):
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     consts = {}
     for m in re.finditer(r'#define\s+(DG_\w+)\s+(\S+)', text):
-        consts[m.group(1)] = int(m.group(2), 0)
+        if re.fullmatch(r'-?(0x[0-9a-fA-F]+|\d+)', m.group(2)):  # (integer constants; the float ones are the kernels' business)
+            consts[m.group(1)] = int(m.group(2), 0)
     for m in re.finditer(r'enum\s*\{(.*?)\}', text, flags=re.S):
         value = -1
         for item in m.group(1).split(','):
@@ -212,7 +213,7 @@ class OpHandle:
 
 class SceneBuilder:
     def __init__(self, timestep=1.0 / 240.0, substeps=2, solver_iterations=150, gravity=(0.0, 0.0, -9.81),
-                 max_episode_steps=None, hot_start=1, rew_mode=0, term_mode=0, max_contacts=None, **overrides):
+                 max_episode_steps=None, hot_start=1, rew_mode=0, term_mode=0, max_contacts=None, hull_manifold_points=1, **overrides):
         self.timestep = float(timestep)
         self.substeps = max(int(substeps), 1)
         self.solver_iterations = int(solver_iterations)
@@ -222,6 +223,11 @@ class SceneBuilder:
         self.rew_mode = rew_mode
         self.term_mode = term_mode
         self.max_contacts = max_contacts
+        # points per hull-hull pair (DG_HF_HULL_MANIFOLD): 1 = the pair's one contact; 2..4 = a one-shot manifold.  A keyword of its
+        # own, not an engine parameter: the CPU checker does not implement it
+        if isinstance(hull_manifold_points, bool) or int(hull_manifold_points) != hull_manifold_points or not 1 <= hull_manifold_points <= 4:
+            raise ValueError('hull_manifold_points must be 1, 2, 3 or 4, got %r' % (hull_manifold_points,))
+        self.hull_manifold_points = int(hull_manifold_points)
         self.params = dict(DEFAULTS)
         for k, v in overrides.items():
             if k not in self.params:
@@ -507,7 +513,7 @@ class SceneBuilder:
 
         # candidate collision pairs: different bodies, at least one of them able to move,
         # and a narrow-phase routine exists for the pair (no box-box)
-        cand, max_contacts, static_pairs = [], 0, 0
+        cand, max_contacts, static_pairs, dyn_hull_pairs = [], 0, 0, False
         coupled = {(k[0][0], k[0][2]) for k in self.constraints}
         for a in range(len(shape_i)):
             for c in range(a + 1, len(shape_i)):
@@ -528,6 +534,10 @@ class SceneBuilder:
                         continue
                 kinds = {ta, tc}
                 per_pair = 4 if kinds == {SHAPE_POINTS, SHAPE_BOX} else 2 if kinds == {SHAPE_CAPSULE, SHAPE_BOX} else 1
+                if kinds == {SHAPE_POINTS} and self.params['hull_contacts'] > 0:
+                    per_pair = self.hull_manifold_points
+                    if shape_dyn[a] and shape_dyn[c]:
+                        dyn_hull_pairs = True
                 max_contacts += per_pair
                 if not (shape_dyn[a] and shape_dyn[c]):
                     static_pairs += per_pair
@@ -549,9 +559,11 @@ class SceneBuilder:
         # Contact budget per env (rows live in LDS).  Default: every contact a moving shape can have
         # with the static world, plus a small pool for moving-vs-moving contacts; `max_contacts`
         # in the env config overrides it.  Contacts beyond the budget are dropped in pair order --
-        # by the oracle and the kernels alike.
+        # by the oracle and the kernels alike.  With a hull manifold (hull_manifold_points = N > 1) a
+        # hull-hull pair counts N and, if two moving bodies can touch hull to hull, so does each slot of the pool.
         n_dyn = sum(1 for b in self.bodies if not (b[0].fixed_base and len(b[0].links) == 0))
-        budget = self.max_contacts if self.max_contacts is not None else max(3, static_pairs + n_dyn)
+        pool = n_dyn * (self.hull_manifold_points if dyn_hull_pairs else 1)
+        budget = self.max_contacts if self.max_contacts is not None else max(3, static_pairs + pool)
         max_contacts = min(max_contacts, int(budget), 32)
 
         def arr(rows, width, dtype):
@@ -655,6 +667,7 @@ class SceneBuilder:
             raise ValueError("motor_impulse_timebase must be 'substep' or 'step'")
         HF[K.HF_HULL_CONTACTS] = p['hull_contacts']
         HF[K.HF_HULL_MARGIN] = p['hull_margin']
+        HF[K.HF_HULL_MANIFOLD] = self.hull_manifold_points
         HF[K.HF_MOTOR_IMPULSE_SCALE] = float(self.substeps) if p['motor_impulse_timebase'] == 'step' else 1.0
         off = K.HF_FLOAT_COUNT
         chunks_f = [HF]

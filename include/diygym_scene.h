@@ -18,7 +18,7 @@
 #define DIYGYM_SCENE_H
 
 #define DG_MAGIC 0x44475953 /* 'DGYS' */
-#define DG_VERSION 13
+#define DG_VERSION 14
 
 /* ---- header ints ---------------------------------------------------- */
 enum {
@@ -125,6 +125,10 @@ enum {
                            btConvexConvexAlgorithm finds per call [R]; 0: through the capsule fitted to each hull (rounds 1-3) */
   DG_HF_HULL_MARGIN,    /* collision margin of a hull shape: the hull is inflated by this radius, i.e. the distance of two hulls
                            is the GJK distance minus twice this (gUrdfDefaultCollisionMargin = 0.001 [R]) */
+  DG_HF_HULL_MANIFOLD,  /* points per hull-hull pair (DIYGym's hull_manifold_points, 1..4; not an engine parameter).  1: the pair's one
+                           contact (GJK / polytope witness midpoint, feature 0).  2..4: a one-shot manifold rebuilt every substep from
+                           that contact's normal -- the two hulls' features along it clipped against each other and reduced to this
+                           many points (dg_hull.h hull_manifold); the CPU checker ignores the slot and keeps its one point */
   DG_HF_FLOAT_COUNT
 };
 
@@ -133,6 +137,13 @@ enum {
  * their rows ended with.  key = candidate pair index * 256 + feature (sphere / fitted capsule: 0; capsule against a box:
  * which end; hull against a box: the hull vertex index).  A reset clears the count. */
 enum { DG_WS_KEY = 0, DG_WS_NORMAL, DG_WS_T1, DG_WS_T2, DG_WS_STRIDE };
+/* A hull-hull manifold point (DG_HF_HULL_MANIFOLD > 1) has feature = its slot 0..3: the chosen points ordered by angle about their
+ * centroid in the plane normal to the contact normal, counted from A's link-frame x axis projected on that plane (y when x is
+ * within 26 degrees of the normal).  A direction fixed to A, not to the points: a box resting on another keeps the same corner
+ * in the same slot from one substep to the next, so its impulses warm-start.  A pair that falls back to its single contact
+ * (a vertex, crossed edges) uses feature 0. */
+#define DG_HULL_MANIFOLD_TOL 0.02f /* a hull point belongs to the feature along the normal if it lies within this x the hull's
+                                      bounding radius of the extreme (~1.1 degrees of tilt across the hull) */
 #define DG_CONTACT_KEY(pair, feature) ((pair) * 256 + ((feature) & 255))  /* exact in fp32 up to 65 536 candidate pairs; hulls of up to 256 points (DIYGym's max_hull_points is capped there) keep one key per vertex */
 
 /* ---- fixed constraints (reference model.py:74-75: p.createConstraint(parent, parent_frame, child, child_frame,
