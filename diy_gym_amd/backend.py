@@ -41,6 +41,8 @@ SYMBOLS = {
     'dg_world_set_render_diag': (ctypes.c_int32, [_vp, ctypes.c_int32]),
     'dg_world_set_diag_buffer': (ctypes.c_int32, [_vp, _vp]),
     'dg_world_set_profile_buffer': (ctypes.c_int32, [_vp, _vp]),
+    'dg_debug_plan': (ctypes.c_int32, [_c_i32p, ctypes.c_int64, _c_f64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _c_i32p, _c_i32p,
+                                       ctypes.c_int64]),
 }
 
 
@@ -69,6 +71,32 @@ def _scene_constants():
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def debug_plan(layout, num_envs, cu_count=256):
+    """What ``dg_world_create`` would decide for ``num_envs`` copies of ``layout``'s scene on a GPU of ``cu_count`` compute
+    units under the environment's ``DG_*`` switches, without a device: a dict keyed by the ``DG_PLAN_*`` names of
+    ``include/diygym_hip.h`` in lower case (``lanes``, ``lds_bytes``, ``par``, ...), plus ``table`` -- the plan table as an
+    int32 array (layout in the header)."""
+    from .scene import _parse_header
+    consts = {k[len('DG_PLAN_'):].lower(): v for k, v in _parse_header(os.path.join(_HERE, '..', 'include', 'diygym_hip.h')).items()
+              if k.startswith('DG_PLAN_')}
+    plan = {k: consts.pop(k) for k in ('plb_stride', 'pll_stride')}   # (constants of the table's layout, not slots)
+    out = np.zeros(consts.pop('count'), dtype=np.int32)
+    lib = load_library()
+    I, F = layout.I, layout.F
+
+    def call(table):
+        rc = lib.dg_debug_plan(I.ctypes.data_as(_c_i32p), I.size, F.ctypes.data_as(_c_f64p), F.size, int(num_envs), int(cu_count),
+                               out.ctypes.data_as(_c_i32p), table.ctypes.data_as(_c_i32p), table.size)
+        if rc != 0:
+            raise RuntimeError('diygym_hip error %d: %s' % (rc, lib.dg_last_error().decode()))
+        return table
+
+    call(np.zeros(0, dtype=np.int32))   # (for the table's length)
+    plan['table'] = call(np.zeros(int(out[consts['table_words']]), dtype=np.int32))
+    plan.update((name, int(out[k])) for name, k in consts.items())
+    return plan
 
 
 class HipBackend:

@@ -18,6 +18,6 @@ struct LaunchTable {
   void (*wrench)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, int link_frame, const float* force, const float* pos, const float* torque, float* gws);
   void (*pose)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int ncam, cip CI, cfp CF, float* table, float* gws);
 };
-const LaunchTable& launch_table(int lanes);  // lanes in {64, 32, 16, 8, 4, 0, -16}
+const LaunchTable& launch_table(int lanes);  // lanes in {64, 32, 16, 8, 4, 1, 0, -16}
 
 }  // namespace dg

@@ -146,6 +146,28 @@ int32_t dg_world_set_diag_buffer(dg_world* w, int32_t* diag);
  * stamps serialise the instruction stream.  Pass NULL (default) for the production kernel. */
 int32_t dg_world_set_profile_buffer(dg_world* w, uint64_t* cycles);
 
+/* Diagnostic, no device needed (the library loads and this call works on a machine without a GPU): what dg_world_create
+ * would decide for `num_envs` copies of the scene blob on a GPU of `cu_count` compute units, under the environment's DG_*
+ * switches -- the same planner, nothing allocated.  plan[DG_PLAN_COUNT] receives the decisions: workspace mode (as dims[7]),
+ * LDS bytes per workgroup, helper-wave kernel, manifold kernels; the LDS plan in slots per env (total, transient region,
+ * contact lists, widest body, total DoF, dense rows, contact row tail, base block of the transient region); the kernel form
+ * (helper body, register-row bodies, narrow-phase wavefronts, split sweeps, early dynamics); floats of the global workspace and
+ * of the hull polytope workspace (0 = not allocated; clamped to INT32_MAX); 1 + last body that is not frozen, 1 + last shape
+ * that is not a box; word offsets of the device-only tables.  `table` (nullable, `table_cap` words) receives the first
+ * plan[DG_PLAN_TABLE_WORDS] words of the plan table:
+ *   per body [DG_PLAN_PLB_STRIDE]: slot of the base rotation (-1: frozen), of M^-1 (nv x nv), of the velocity change (nv), nv,
+ *                                  1 for a fixed-base serial chain of <= 6 joints;
+ *   per link [DG_PLAN_PLL_STRIDE]: slot of the pose (9), of the motor / limit rows (6), of the inertia accumulator (21, inside
+ *                                  the transient region) or -1;
+ *   then at DG_PLAN_PD_OFF / GD_OFF / SD_OFF / AM_OFF the pair, group and shape descriptors and the ancestor masks. */
+enum { DG_PLAN_LANES = 0, DG_PLAN_LDS_BYTES, DG_PLAN_PAR, DG_PLAN_MF, DG_PLAN_TOTAL_SLOTS, DG_PLAN_TR_OFF, DG_PLAN_TR_SLOTS, DG_PLAN_CONT_OFF,
+       DG_PLAN_CONT2_OFF, DG_PLAN_NV_MAX, DG_PLAN_NT, DG_PLAN_DENSE, DG_PLAN_CROW_TAIL, DG_PLAN_AB_STRIDE, DG_PLAN_HELPER_BODY, DG_PLAN_REG_BODY0,
+       DG_PLAN_REG_BODY1, DG_PLAN_COLL_WAVE, DG_PLAN_COLL_SPLIT, DG_PLAN_SPLIT_PGS, DG_PLAN_EARLY_DYN, DG_PLAN_GWS_FLOATS, DG_PLAN_HULL_WS_FLOATS,
+       DG_PLAN_NBA, DG_PLAN_NSHA, DG_PLAN_PD_OFF, DG_PLAN_GD_OFF, DG_PLAN_SD_OFF, DG_PLAN_AM_OFF, DG_PLAN_TABLE_WORDS, DG_PLAN_COUNT };
+enum { DG_PLAN_PLB_STRIDE = 5, DG_PLAN_PLL_STRIDE = 3 };
+int32_t dg_debug_plan(const int32_t* idata, int64_t n_i, const double* fdata, int64_t n_f, int32_t num_envs, int32_t cu_count,
+                      int32_t* plan, int32_t* table, int64_t table_cap);
+
 #ifdef __cplusplus
 }
 #endif
