@@ -225,7 +225,7 @@ int plan_world(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int 
     plan.push_back(sa | (sb << 12) | (ta << 24) | (tb << 26) | ((swap ? 1 : 0) << 28));
   }
   // group descriptors (broad phase), device-only: centre and reach of the group's static shape when that shape is frozen in
-  // the world -- [x y z reach], reach = bound of the moving body + margin + extent of the shape; reach < 0: the narrow
+  // the world -- [x y z reach], reach = bound of the moving body + margin (+ hull margins) + extent of the shape; reach < 0: the narrow
   // phase works the group's bounds out from the tables (a moving partner)
   out.gd_off = plan.size();
   { const int32_t* GIh = I + I[DG_H_OFF_GROUP_I]; const double* SFh = F + I[DG_H_OFF_SHAPE_F]; const double* BFh = F + I[DG_H_OFF_BODY_F];
@@ -234,9 +234,11 @@ int plan_world(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int 
       if (ss >= 0 && (SIh[ss * DG_SI_STRIDE + DG_SI_FLAGS] & DG_SHAPE_WORLD)) {
         const double* sf = SFh + ss * DG_SF_STRIDE; const int st = SIh[ss * DG_SI_STRIDE + DG_SI_TYPE];
         const float p0 = (float)sf[DG_SF_PARAMS], p1 = (float)sf[DG_SF_PARAMS + 1], p2 = (float)sf[DG_SF_PARAMS + 2];
-        const float ext = st == DG_SHAPE_SPHERE ? p0 : st == DG_SHAPE_BOX ? sqrtf(p0 * p0 + p1 * p1 + p2 * p2) : p0 + p1;
+        // (a hull: p2 = the radius around the fitted capsule's centre that holds its points; r + half alone lets points near the caps stick out)
+        const float ext = st == DG_SHAPE_SPHERE ? p0 : st == DG_SHAPE_BOX ? sqrtf(p0 * p0 + p1 * p1 + p2 * p2) : st == DG_SHAPE_POINTS ? fmaxf(p0 + p1, p2) : p0 + p1;
         d[0] = (float)sf[DG_SF_POS]; d[1] = (float)sf[DG_SF_POS + 1]; d[2] = (float)sf[DG_SF_POS + 2];
-        d[3] = (float)BFh[gi[DG_GI_BODY_A] * DG_BF_STRIDE + DG_BF_BOUND] + (float)F[DG_HF_CONTACT_MARGIN] + ext;
+        // (+ the two hull margins where hulls collide as hulls: their contacts exist out to margin + 2 x hull margin)
+        d[3] = (float)BFh[gi[DG_GI_BODY_A] * DG_BF_STRIDE + DG_BF_BOUND] + (float)F[DG_HF_CONTACT_MARGIN] + (F[DG_HF_HULL_CONTACTS] > 0 ? 2.f * (float)F[DG_HF_HULL_MARGIN] : 0.f) + ext;
       }
       for (int k = 0; k < 4; k++) { int32_t bits; memcpy(&bits, &d[k], 4); plan.push_back(bits); }
     } }

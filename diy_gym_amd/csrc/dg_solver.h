@@ -123,6 +123,8 @@ template <int LANES, int TBL, int SLC = 1>
 DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff, int list = -1, int sl = 0) {
   const DevScene& sc = ln.sc; int cnt = 0; const float margin = sc.HF[DG_HF_CONTACT_MARGIN];
   const bool hull_mode = sc.HF[DG_HF_HULL_CONTACTS] > 0.f; const float hmg = sc.HF[DG_HF_HULL_MARGIN];
+  // distance term of the group tests: two hulls that collide as hulls report contacts out to margin + 2 x hull margin
+  const float gmargin = margin + (hull_mode ? 2.f * hmg : 0.f);
   if (list < 0) list = sc.cont_off;
   if (sc.npairs == 0) { ln.L(list) = 0.f; return 0; }
   for (int sh = 0; sh < sc.nsha; sh++) {
@@ -131,8 +133,9 @@ DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff
     if (type != DG_SHAPE_SPHERE) seg_ends(w, e0, e1);
     const int o = sc.tr_off + sh * SC_STRIDE;
     ln.L3set(o + SC_C, (e0 + e1) * 0.5f); ln.L3set(o + SC_H, (e1 - e0) * 0.5f); ln.L(o + SC_R) = w.prm0;
-    // (a hull's fitted capsule lets hull points near its caps stick out: with hull contacts the bound is the sphere that holds them all)
-    ln.L(o + SC_BOUND) = (hull_mode && type == DG_SHAPE_POINTS) ? fmaxf(w.prm0 + w.prm1, w.prm2) : w.prm0 + (type == DG_SHAPE_SPHERE ? 0.f : w.prm1);
+    // (a hull's fitted capsule lets hull points near its caps stick out: the bound of a hull is the sphere that holds them all and the
+    // capsule -- in both hull_contacts modes: the hull-against-box culls below test the POINTS against this sphere either way)
+    ln.L(o + SC_BOUND) = type == DG_SHAPE_POINTS ? fmaxf(w.prm0 + w.prm1, w.prm2) : w.prm0 + (type == DG_SHAPE_SPHERE ? 0.f : w.prm1);
   }
   // broad phase: a group = all pairs between one moving body and one shape of the static world (or another
   // moving body); skipped as a whole when the bounding spheres are apart in every lane of the wave
@@ -161,10 +164,11 @@ DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff
       const V3 dc = cpos - v3(ox, oy, oz); if (!__any(dot(dc, dc) < orr * orr)) continue;
     } else {
       const int bb = gi[DG_GI_BODY_B], ss = gi[DG_GI_STATIC_SHAPE];
-      V3 other; float reach = sc.BF[ba * DG_BF_STRIDE + DG_BF_BOUND] + margin;
+      V3 other; float reach = sc.BF[ba * DG_BF_STRIDE + DG_BF_BOUND] + gmargin;
       if (ss >= 0) {
         cip si = sc.SI + ss * DG_SI_STRIDE; cfp sf = sc.SF + ss * DG_SF_STRIDE; const int st = si[DG_SI_TYPE];
-        reach += st == DG_SHAPE_SPHERE ? sf[DG_SF_PARAMS] : st == DG_SHAPE_BOX ? sqrtf(sf[DG_SF_PARAMS] * sf[DG_SF_PARAMS] + sf[DG_SF_PARAMS + 1] * sf[DG_SF_PARAMS + 1] + sf[DG_SF_PARAMS + 2] * sf[DG_SF_PARAMS + 2]) : sf[DG_SF_PARAMS] + sf[DG_SF_PARAMS + 1];
+        const float p0 = sf[DG_SF_PARAMS], p1 = sf[DG_SF_PARAMS + 1], p2 = sf[DG_SF_PARAMS + 2];  // (a hull: p2 = the radius that holds its points, as in SC_BOUND)
+        reach += st == DG_SHAPE_SPHERE ? p0 : st == DG_SHAPE_BOX ? sqrtf(p0 * p0 + p1 * p1 + p2 * p2) : st == DG_SHAPE_POINTS ? fmaxf(p0 + p1, p2) : p0 + p1;
         if (si[DG_SI_FLAGS] & DG_SHAPE_WORLD) other = v3(sf[DG_SF_POS], sf[DG_SF_POS + 1], sf[DG_SF_POS + 2]);
         else { WShape w; shape_world(ln, ss, w); other = w.p; }
       } else { other = ln.base_pos(bb); reach += sc.BF[bb * DG_BF_STRIDE + DG_BF_BOUND]; }

@@ -181,6 +181,31 @@ def shape_bound(sh):
     return 0.0
 
 
+def report_distance(params, kind_a, kind_c):
+    """Largest distance of two shapes at which the narrow phase still reports a contact: the contact margin, plus the two
+    hull margins when the pair collides hull against hull (hull_contacts > 0; the GJK distance has both subtracted)."""
+    both_hulls = kind_a == SHAPE_POINTS and kind_c == SHAPE_POINTS and params['hull_contacts'] > 0
+    return float(params['contact_margin']) + (2.0 * float(params['hull_margin']) if both_hulls else 0.0)
+
+
+def statically_apart(anchor_a, anchor_c, reach, slack=1e-3):
+    """Static pruning: True when two shapes of bolted-down bodies can never come within ``reach`` of each other.  An anchor
+    is (centre, radius) of a sphere that holds the shape in every reachable configuration, or None (the base can move)."""
+    if anchor_a is None or anchor_c is None:
+        return False
+    (ca, ra), (cc, rc) = anchor_a, anchor_c
+    return bool(np.linalg.norm(ca - cc) - ra - rc > reach + slack)
+
+
+def points_extent(pts, origin=None):
+    """Radius around ``origin`` (default: the frame's own) that holds a hull as the narrow phase sees it: its points, and
+    the capsule fitted to them (what a sphere, a capsule or -- with hull_contacts = 0 -- another hull collides with)."""
+    pts = np.asarray(pts, dtype=np.float64) - (0.0 if origin is None else np.asarray(origin, dtype=np.float64))
+    T, r, half = fit_capsule(pts)
+    ends = max(float(np.linalg.norm(T.p - T.R[:, 2] * half)), float(np.linalg.norm(T.p + T.R[:, 2] * half)))
+    return max(float(np.max(np.linalg.norm(pts, axis=1))), ends + r)
+
+
 def body_bound(flat):
     """Conservative radius around the base origin that contains every collision shape of the body whatever the
     joint angles: joint offsets (and prismatic travel) add up along the chain."""
@@ -194,7 +219,7 @@ def body_bound(flat):
     for sh in flat.shapes:
         base = reach[sh.link] if sh.link >= 0 else 0.0
         if sh.kind == SHAPE_POINTS:
-            ext = float(np.max(np.linalg.norm(np.asarray(sh.points), axis=1)))
+            ext = points_extent(sh.points)
         else:
             ext = float(np.linalg.norm(sh.T.p)) + shape_bound(sh)
         out = max(out, base + ext)
@@ -486,11 +511,11 @@ class SceneBuilder:
                     shape_anchor.append(None)
                 elif frozen:
                     c = np.asarray(T.p, dtype=np.float64)
-                    rad = float(np.max(np.linalg.norm(pts - c, axis=1))) if pts is not None else float(
+                    rad = points_extent(pts, c) if pts is not None else float(
                         prm[0] if kind == SHAPE_SPHERE else np.linalg.norm(prm) if kind == SHAPE_BOX else prm[0] + prm[1])
                     shape_anchor.append((c, rad))
                 else:
-                    ext = float(np.max(np.linalg.norm(pts, axis=1))) if pts is not None else float(np.linalg.norm(T.p)) + float(
+                    ext = points_extent(pts) if pts is not None else float(np.linalg.norm(T.p)) + float(
                         prm[0] if kind == SHAPE_SPHERE else np.linalg.norm(prm) if kind == SHAPE_BOX else prm[0] + prm[1])
                     shape_anchor.append((np.asarray(p_link, dtype=np.float64), (link_reach[sh.link] if sh.link >= 0 else 0.0) + ext))
         addon_off = state_off
@@ -513,7 +538,7 @@ class SceneBuilder:
 
         # candidate collision pairs: different bodies, at least one of them able to move,
         # and a narrow-phase routine exists for the pair (no box-box)
-        cand, max_contacts, static_pairs, dyn_hull_pairs = [], 0, 0, False
+        cand, max_contacts, static_pairs, dyn_hull_pairs, pruned = [], 0, 0, False, []
         coupled = {(k[0][0], k[0][2]) for k in self.constraints}
         for a in range(len(shape_i)):
             for c in range(a + 1, len(shape_i)):
@@ -528,10 +553,9 @@ class SceneBuilder:
                     continue
                 # static pruning: two shapes whose bases are bolted down can be too far apart to ever touch
                 # (the shoulders of two arms a metre apart); such a pair can produce no contact in any backend
-                if shape_anchor[a] is not None and shape_anchor[c] is not None:
-                    (ca, ra), (cc, rc) = shape_anchor[a], shape_anchor[c]
-                    if np.linalg.norm(ca - cc) - ra - rc > self.params['contact_margin'] + 1e-3:
-                        continue
+                if statically_apart(shape_anchor[a], shape_anchor[c], report_distance(self.params, ta, tc)):
+                    pruned.append((a, c))
+                    continue
                 kinds = {ta, tc}
                 per_pair = 4 if kinds == {SHAPE_POINTS, SHAPE_BOX} else 2 if kinds == {SHAPE_CAPSULE, SHAPE_BOX} else 1
                 if kinds == {SHAPE_POINTS} and self.params['hull_contacts'] > 0:
@@ -678,6 +702,8 @@ class SceneBuilder:
         I = np.ascontiguousarray(np.concatenate(chunks_i).astype(np.int32))
         F = np.ascontiguousarray(np.concatenate(chunks_f).astype(np.float64))
         layout = SceneLayout(self, I, F, body_i, link_state_offs, addon_off, state_dim, max_contacts)
+        # what the static pruning decided, for tests: the shape pairs it removed and the anchor of every shape
+        layout.pruned_pairs, layout.shape_anchors = pruned, shape_anchor
         return layout
 
 
