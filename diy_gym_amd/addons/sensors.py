@@ -211,3 +211,76 @@ class Camera(Addon):
         if self.use_seg_mask:
             obs['segmentation_mask'] = env._out(seg)
         return obs
+
+
+class Lidar(Addon):
+    """Range scan by batched ray casting against the collision geometry (``env.sim.ray_test_batch`` -- pybullet's
+    ``p.rayTestBatch``; the reference ships no such addon).  Attaches to a model frame or to the world exactly like
+    ``camera`` (``frame``, ``xyz``, ``rpy``).  Sensor frame: x forward, z up; azimuth turns about z, elevation tilts
+    towards z.  Config keys: ``num_rays`` 64 (per ring), ``num_rings`` 1, ``horizontal_fov`` [-180, 180] degrees (the end
+    is left out when the fan spans 360 degrees: no doubled ray), ``vertical_fov`` [0, 0] degrees (the rings' elevations),
+    ``range`` [0.05, 10.0] (rays run from ``min`` to ``max`` along each direction), ``ignore_parent`` True (no ray can hit
+    the model the sensor sits on), ``use_ids`` False.
+
+    * ``ranges`` ``[num_rings, num_rays]``: metres from the sensor origin to the nearest surface, ``max`` where nothing is hit.
+    * ``ids`` (with ``use_ids``) int32, same shape: ``uid + ((link + 1) << 24)`` as the camera's segmentation mask, -1 = nothing.
+
+    Evaluated by its own two kernel launches (``dg_world_raycast``), lazily, the first time ``observe()`` is called after a step."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        from ..mathx import Transform, quat_from_euler
+        from ..model import Model
+        self.num_rays = int(config.get('num_rays', 64))
+        self.num_rings = int(config.get('num_rings', 1))
+        self.horizontal_fov = [float(v) for v in config.get('horizontal_fov', [-180., 180.])]
+        self.vertical_fov = [float(v) for v in config.get('vertical_fov', [0., 0.])]
+        self.range_min, self.range_max = (float(v) for v in config.get('range', [0.05, 10.0]))
+        if self.num_rays < 1 or self.num_rings < 1 or not 0.0 <= self.range_min < self.range_max:
+            raise ValueError('lidar: num_rays and num_rings must be >= 1 and range [min, max] must satisfy 0 <= min < max')
+        self.uid = parent.uid if isinstance(parent, Model) else -1
+        self.frame_id = parent.get_frame_id(config.get('frame')) if 'frame' in config else -1
+        self.ignore_parent = bool(config.get('ignore_parent', True))
+        self.use_ids = bool(config.get('use_ids', False))
+        T = Transform.from_xyz_quat(config.get('xyz', [0., 0., 0.]), quat_from_euler(config.get('rpy', [0., 0., 0.])))
+        self.T_parent_sensor = T
+        # ray directions, built once: [num_rings * num_rays, 3] in the sensor frame, then the segments in the parent frame
+        lo, hi = self.horizontal_fov
+        n = self.num_rays
+        if abs(hi - lo) >= 360.0 - 1e-9:
+            az = lo + (hi - lo) * np.arange(n) / n
+        else:
+            az = np.linspace(lo, hi, n)
+        el = np.linspace(self.vertical_fov[0], self.vertical_fov[1], self.num_rings)
+        az, el = np.radians(az)[None, :], np.radians(el)[:, None]
+        dirs = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el) * np.ones_like(az)], axis=-1).reshape(-1, 3)
+        self.directions = dirs
+        self.ray_from = (T.p[None, :] + (dirs * self.range_min) @ T.R.T).astype(np.float32)
+        self.ray_to = (T.p[None, :] + (dirs * self.range_max) @ T.R.T).astype(np.float32)
+        shape = [self.num_rings, self.num_rays]
+        sp = OrderedDict(ranges=spaces.Box(0., self.range_max, shape=shape, dtype='float32'))
+        if self.use_ids:
+            sp['ids'] = spaces.Box(-1, np.iinfo(np.int32).max, shape=shape, dtype='int32')
+        self.observation_space = spaces.Dict(sp)
+        self.own_buffers = True   # like a camera's pictures, the scan is not part of the kernel's observation rows
+        self._tick = None
+        self._rays = None
+
+    def compile(self, builder):
+        pass   # rays are run-time arguments of dg_world_raycast: nothing in the scene blob
+
+    def observe(self):
+        import torch
+        env = self.env
+        if self._rays is None:
+            self._rays = (torch.as_tensor(self.ray_from, device=env.device).contiguous(), torch.as_tensor(self.ray_to, device=env.device).contiguous())
+        if self._tick != env._tick:
+            hits = env.sim.ray_test_batch(self._rays[0], self._rays[1], body=self.uid, frame=self.frame_id,
+                                          skip_body=self.uid if self.ignore_parent else -1, want=('frac', 'id') if self.use_ids else ('frac', ))
+            shape = (env.num_envs, self.num_rings, self.num_rays)
+            self._ranges = (self.range_min * (1.0 - hits.frac) + self.range_max * hits.frac).reshape(shape)   # (frac = 1, a miss: max exactly)
+            self._ids = hits.id.reshape(shape).clone() if self.use_ids else None   # (the backend reuses its output tensors)
+            self._tick = env._tick
+        obs = OrderedDict(ranges=env._out(self._ranges))
+        if self.use_ids:
+            obs['ids'] = env._out(self._ids)
+        return obs

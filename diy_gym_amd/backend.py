@@ -5,6 +5,7 @@ HIP library has not been built, or no GPU is visible, constructing a backend
 raises.  (The CPU oracle under ``oracle/`` is test infrastructure and is never
 imported from here.)
 """
+import collections
 import ctypes
 import os
 
@@ -38,6 +39,9 @@ SYMBOLS = {
     'dg_world_frame_state': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     'dg_world_apply_wrench': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]),
     'dg_world_render': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    'dg_world_raycast_scratch_floats': (ctypes.c_int64, [_vp]),
+    'dg_world_raycast': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp,
+                                          _vp, _vp, _vp, _vp, _vp]),
     'dg_world_set_render_diag': (ctypes.c_int32, [_vp, ctypes.c_int32]),
     'dg_world_set_diag_buffer': (ctypes.c_int32, [_vp, _vp]),
     'dg_world_set_profile_buffer': (ctypes.c_int32, [_vp, _vp]),
@@ -71,6 +75,10 @@ def _scene_constants():
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+# what ray_test_batch returns: device tensors, None for the outputs `want` left out
+RayHits = collections.namedtuple('RayHits', ['frac', 'id', 'pos', 'normal'])
 
 
 def debug_plan(layout, num_envs, cu_count=256):
@@ -133,6 +141,7 @@ class HipBackend:
             self.term = torch.zeros((B, max(self.term_dim, 1)), dtype=torch.uint8, device=dev)
             self.rew_sum = torch.zeros((B, ), dtype=torch.float32, device=dev)
             self.term_flag = torch.zeros((B, ), dtype=torch.uint8, device=dev)
+        self._ray_scratch, self._ray_out = None, {}   # ray_test_batch: the pose scratch and the output buffers per `want`
         self._check(self.lib.dg_world_init_state(self.handle, _ptr(self.state), self._stream()))
 
     def _stream(self):
@@ -263,6 +272,50 @@ class HipBackend:
         if seg is not None:
             self._require_numel('seg', seg, px, torch.int32)
         self._check(self.lib.dg_world_render(self.handle, _ptr(self.state), int(camera), _ptr(rgb), _ptr(depth), _ptr(seg), self._stream()))
+
+    # -- batched p.rayTestBatch ------------------------------------------------------------------------------------------
+    def ray_test_batch(self, ray_from, ray_to, body=-1, frame=-1, skip_body=-1, want=('frac', 'id', 'pos', 'normal')):
+        """``p.rayTestBatch(rayFromPositions, rayToPositions)`` for every env at once: ``ray_from`` / ``ray_to`` are float32
+        ``[N, 3]`` (the same rays in every env) or ``[B, N, 3]`` (rays of their own per env) on this device -- in world
+        coordinates, or with ``body`` (a Model's ``uid``) in the frame ``frame`` of that model (the index
+        ``Model.get_frame_id`` returns, -1: the base), which is what a sensor riding on a link wants.  ``skip_body``: a
+        model no ray can hit (the sensor's own).  Returns ``RayHits(frac, id, pos, normal)``: ``[B, N]`` hit fraction (1.0 =
+        nothing hit), ``[B, N]`` int32 ``uid + ((link + 1) << 24)`` (-1 = nothing hit), ``[B, N, 3]`` world hit position
+        (``ray_to`` on a miss) and ``[B, N, 3]`` world unit normal (0 on a miss); those not named in ``want`` are None.  The
+        tensors are views of buffers kept per ``want`` (grown to the largest N seen) and REUSED by the next call: clone what must last.
+        See ``dg_world_raycast`` for the semantics."""
+        B = self.num_envs
+        if not isinstance(ray_from, torch.Tensor) or not isinstance(ray_to, torch.Tensor):
+            raise ValueError('ray_from and ray_to must be torch.Tensors')
+        if ray_from.dim() not in (2, 3) or ray_from.shape[-1] != 3 or ray_from.shape[-2] < 1:
+            raise ValueError('ray_from must have shape [N, 3] or [%d, N, 3] with N >= 1, got %s' % (B, tuple(ray_from.shape)))
+        per_env, n = ray_from.dim() == 3, int(ray_from.shape[-2])
+        shape = (B, n, 3) if per_env else (n, 3)
+        self._require('ray_from', ray_from, shape, torch.float32)
+        self._require('ray_to', ray_to, shape, torch.float32)
+        unknown = set(want) - set(RayHits._fields)
+        if unknown or 'frac' not in want:
+            raise ValueError("want must name 'frac' and any of 'id', 'pos', 'normal', got %r" % (want, ))
+        if body >= 0:
+            body, frame = self.layout.resolve_frame(body, frame)
+        if skip_body >= 0:
+            skip_body = self.layout.resolve_frame(skip_body, -1)[0]
+        # one set of flat output buffers per `want`, grown to the largest N seen; the [B, N] results are views of their heads
+        key = tuple(f in want for f in RayHits._fields)
+        if self._ray_scratch is None:
+            self._ray_scratch = torch.empty((max(int(self.lib.dg_world_raycast_scratch_floats(self.handle)), 1), ), dtype=torch.float32, device=self.device)
+        if key not in self._ray_out or self._ray_out[key][0].numel() < B * n:
+            self._ray_out[key] = (torch.empty((B * n, ), dtype=torch.float32, device=self.device),
+                                  torch.empty((B * n, ), dtype=torch.int32, device=self.device) if key[1] else None,
+                                  torch.empty((B * n * 3, ), dtype=torch.float32, device=self.device) if key[2] else None,
+                                  torch.empty((B * n * 3, ), dtype=torch.float32, device=self.device) if key[3] else None)
+        f_, i_, p_, n_ = self._ray_out[key]
+        out = RayHits(f_[:B * n].view(B, n), None if i_ is None else i_[:B * n].view(B, n), None if p_ is None else p_[:3 * B * n].view(B, n, 3),
+                      None if n_ is None else n_[:3 * B * n].view(B, n, 3))
+        self._check(self.lib.dg_world_raycast(self.handle, _ptr(self.state), int(body), int(frame), n, _ptr(ray_from), _ptr(ray_to), int(per_env),
+                                              int(skip_body), _ptr(self._ray_scratch), _ptr(out.frac), _ptr(out.id), _ptr(out.pos), _ptr(out.normal),
+                                              self._stream()))
+        return out
 
     def set_render_diag(self, flags):
         """Diagnostic switches of ``render`` (1: no culling -- the brute-force picture; see dg_world_set_render_diag)."""

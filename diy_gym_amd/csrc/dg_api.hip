@@ -16,6 +16,7 @@
 #include "dg_plan.h"
 #define DG_DEFINE_RENDER_KERNEL
 #include "dg_render.h"
+#include "dg_raycast.h"
 
 using namespace dg;
 
@@ -77,6 +78,8 @@ struct dg_world {
   int cu_count = 1;     // multiProcessorCount of `device`, read once in dg_world_create
   int render_diag = 0;  // the plan's at creation (DG_RENDER_NO_CULL / DG_RENDER_DIAG, diagnostics), dg_world_set_render_diag later
   int render_wpe = 2;   // wavefronts per SIMD of the render kernel's build (DG_RENDER_WPE=3: the spilling build)
+  int ray_no_cull = 0;  // dg_debug_raycast_no_cull, for tests: every ray against every shape
+  int ray_lds_words = DG_RAY_LDS_WORDS;  // LDS budget of raycast_kernel's staged rows (dg_debug_raycast_lds_words, for tests)
   int ncam = 0; float* d_render_table = nullptr; cip d_CI = nullptr; cfp d_CF = nullptr, d_PLN = nullptr;
   ~dg_world() {  // also the clean-up of a dg_world_create that failed half way
     DeviceGuard g(device);
@@ -86,7 +89,7 @@ struct dg_world {
 
 extern "C" {
 
-int32_t dg_version(void) { return (0 << 16) | 6; }
+int32_t dg_version(void) { return (0 << 16) | 7; }
 const char* dg_last_error(void) { return g_err.c_str(); }
 
 int32_t dg_world_create(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int32_t num_envs, int32_t env_stride,
@@ -243,7 +246,7 @@ int32_t dg_world_render(dg_world* w, const float* state, int32_t camera, float* 
   if (!w || !state) return fail(DG_ERR_ARG, "null argument");
   if (camera < 0 || camera >= w->ncam) return fail(DG_ERR_ARG, "camera %d out of range (scene has %d)", camera, w->ncam);
   DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).pose(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), w->ncam, w->d_CI, w->d_CF, w->d_render_table, w->d_gws);
+  launch_table(w->lanes, w->mf).pose(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), w->ncam, w->d_CI, w->d_CF, w->d_render_table, w->d_gws, 0, -1, -1);
   HIP_TRY(hipGetLastError());
   const int32_t* I = w->I.data(); const int32_t* ci = I + I[DG_H_OFF_CAMERA_I] + camera * DG_CI_STRIDE;
   // Rows per workgroup: a multiple of 8 (the tile height of render_kernel's wavefronts; 200-wide images: whole cache lines).
@@ -271,6 +274,64 @@ int32_t dg_world_render(dg_world* w, const float* state, int32_t camera, float* 
                      (cfp)w->d_render_table, rgb, depth, seg, band_rows, nbands, w->render_diag);
   }
   HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// floats per env of dg_world_raycast's scratch: the shape rows of pose_kernel and the mount row
+static size_t raycast_row_floats(const dg_world* w) { return (size_t)w->sc.nsh * RS_STRIDE + RC_STRIDE; }
+
+int64_t dg_world_raycast_scratch_floats(const dg_world* w) {
+  if (!w) { (void)fail(DG_ERR_ARG, "null world"); return 0; }
+  return (int64_t)((size_t)w->num_envs * raycast_row_floats(w));
+}
+
+int32_t dg_world_raycast(dg_world* w, const float* state, int32_t body, int32_t frame, int32_t n_rays, const float* ray_from, const float* ray_to,
+                         int32_t per_env, int32_t skip_body, float* scratch, float* frac, int32_t* id, float* pos, float* normal, void* stream) {
+  if (!w || !state || !ray_from || !ray_to) return fail(DG_ERR_ARG, "null argument");
+  if (n_rays <= 0) return fail(DG_ERR_ARG, "n_rays must be positive, got %d", n_rays);
+  if (!frac) return fail(DG_ERR_ARG, "frac is NULL (id, pos and normal may be)");
+  if (!scratch) return fail(DG_ERR_ARG, "scratch is NULL (dg_world_raycast_scratch_floats floats of device memory)");
+  if (body < -1 || body >= w->sc.nb) return fail(DG_ERR_ARG, "body %d out of range", body);
+  if (skip_body < -1 || skip_body >= w->sc.nb) return fail(DG_ERR_ARG, "skip_body %d out of range", skip_body);
+  if (body < 0 && frame != -1) return fail(DG_ERR_ARG, "frame %d given without a body", frame);
+  if (frame < -1) return fail(DG_ERR_ARG, "frame %d out of range", frame);
+  int gf = -1;  // `frame` is the body-local pybullet joint index; the kernels use the global frame index
+  if (frame >= 0) {
+    const int32_t* I = w->I.data(); const int32_t* FI = I + I[DG_H_OFF_FRAME_I]; int seen = 0; bool found = false;
+    for (int f = 0; f < w->sc.nfr; f++) if (FI[f * DG_FI_STRIDE + DG_FI_BODY] == body) { if (seen == frame) { gf = f; found = true; break; } seen++; }
+    if (!found) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
+  }
+  // one workgroup per (env, chunk of rays): a wavefront per 64 rays, at most four of them
+  const int threads = 64 * std::min(4, (n_rays + 63) / 64), nchunks = (n_rays + threads - 1) / threads;
+  const long long blocks = (long long)nchunks * w->num_envs;  // the env index is folded into grid.x
+  if (blocks > 0x7fffffffLL) return fail(DG_ERR_UNSUPPORTED, "raycast: %lld workgroups exceed the grid limit", blocks);
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).pose(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), 0, w->d_CI, w->d_CF, scratch, w->d_gws, 1, body, gf);
+  HIP_TRY(hipGetLastError());
+  const int words = w->sc.nsh * RY_STRIDE;
+  if (words <= w->ray_lds_words)
+    hipLaunchKernelGGL(raycast_kernel<true>, dim3((unsigned)blocks), dim3(threads), sizeof(float) * (size_t)words, (hipStream_t)stream, w->sc, w->d_PLN, (cfp)scratch, n_rays, nchunks,
+                       ray_from, ray_to, per_env != 0, body >= 0, skip_body, w->ray_no_cull, frac, id, pos, normal);
+  else
+    hipLaunchKernelGGL(raycast_kernel<false>, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, w->sc, w->d_PLN, (cfp)scratch, n_rays, nchunks,
+                       ray_from, ray_to, per_env != 0, body >= 0, skip_body, w->ray_no_cull, frac, id, pos, normal);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// diagnostics: the LDS budget (in 4-byte words, at most DG_RAY_LDS_WORDS) of dg_world_raycast's staged shape rows; 0 sends every
+// scene through the table-reading form of the kernel -- tests compare the two; not part of the public header
+int32_t dg_debug_raycast_lds_words(dg_world* w, int32_t words) {
+  if (!w || words < 0 || words > DG_RAY_LDS_WORDS) return fail(DG_ERR_ARG, "dg_debug_raycast_lds_words: bad argument");
+  w->ray_lds_words = words;
+  return DG_OK;
+}
+
+// diagnostics: dg_world_raycast without its bounding-sphere rejects (what the culled call must equal bit for bit); not part of the
+// public header
+int32_t dg_debug_raycast_no_cull(dg_world* w, int32_t on) {
+  if (!w) return fail(DG_ERR_ARG, "null world");
+  w->ray_no_cull = on != 0;
   return DG_OK;
 }
 

@@ -66,8 +66,8 @@ static void l_frame(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable 
 static void l_wrench(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, int link_frame, const float* force, const float* pos, const float* torque, float* gws) {
   hipLaunchKernelGGL(wrench_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, frame, link_frame, force, pos, torque, gws);
 }
-static void l_pose(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int ncam, cip CI, cfp CF, float* table, float* gws) {
-  hipLaunchKernelGGL(pose_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, ncam, CI, CF, table, gws);
+static void l_pose(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int ncam, cip CI, cfp CF, float* table, float* gws, int nmount, int mbody, int mframe) {
+  hipLaunchKernelGGL(pose_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, ncam, CI, CF, table, gws, nmount, mbody, mframe);
 }
 static hipError_t l_prepare(int lds) {
   if (L == 0) return hipSuccess;

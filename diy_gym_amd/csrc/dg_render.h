@@ -17,7 +17,8 @@ namespace dg {
 enum { RS_R = 0, RS_P = 9, RS_C = 12, RS_BOUND = 15, RS_COLOR = 16 /* this env's texture of the shape (DG_TX_*): colour A, colour B, frequency, kind */, RS_STRIDE = 24, RC_STRIDE = 12 };
 
 template <int LANES>
-__global__ __launch_bounds__(64) void pose_kernel(DevScene sc, MotorTable mt, float* state, int ncam, cip CI, cfp CF, float* table, float* gws) {
+__global__ __launch_bounds__(64) void pose_kernel(DevScene sc, MotorTable mt, float* state, int ncam, cip CI, cfp CF, float* table, float* gws,
+                                                   int nmount, int mbody, int mframe) {  // nmount 1 (dg_world_raycast): one more RC row, the pose of frame `mframe` of `mbody`
   extern __shared__ float smem[];
   constexpr int ACTIVE = envs_per_wave(LANES);
   // the 64 / ACTIVE lanes that a narrow mode leaves idle per env share the env's shapes: each of them runs the (cheap, serial)
@@ -27,7 +28,7 @@ __global__ __launch_bounds__(64) void pose_kernel(DevScene sc, MotorTable mt, fl
   const int env = blockIdx.x * ACTIVE + lane; if (env >= sc.num_envs) return;
   Lane<LANES> ln(sc, mt, workspace_of<LANES>(sc, smem, gws, lane), state + env, env, false);
   for (int b = 0; b < sc.nba; b++) ln.kinematics(b);
-  float* out = table + (size_t)env * (sc.nsh * RS_STRIDE + ncam * RC_STRIDE);
+  float* out = table + (size_t)env * (sc.nsh * RS_STRIDE + (ncam + nmount) * RC_STRIDE);
   for (int sh = sub; sh < sc.nsh; sh += GROUP) {
     WShape w; shape_world(ln, sh, w); cip si = sc.SI + sh * DG_SI_STRIDE; float* o = out + sh * RS_STRIDE;
     M3 R = w.R; V3 p = w.p; float bound;
@@ -54,6 +55,14 @@ __global__ __launch_bounds__(64) void pose_kernel(DevScene sc, MotorTable mt, fl
 #pragma unroll
     for (int k = 0; k < 9; k++) o[k] = Rc.m[k];
     o[9] = pc.x; o[10] = pc.y; o[11] = pc.z;
+  }
+  if (nmount && sub == 0) {  // the frame rays are given in (as a camera's parent frame above); mbody < 0: the world
+    M3 Rp = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}}; V3 pp = v3(0.f, 0.f, 0.f);
+    if (mbody >= 0) { V3 v, w; Q4 q; ln.frame_state(mbody, mframe, mframe < 0, pp, q, v, w, false); Rp = qmat(q); }
+    float* o = out + sc.nsh * RS_STRIDE + ncam * RC_STRIDE;
+#pragma unroll
+    for (int k = 0; k < 9; k++) o[k] = Rp.m[k];
+    o[9] = pp.x; o[10] = pp.y; o[11] = pp.z;
   }
 }
 

@@ -119,7 +119,9 @@ class DIYGym(Receptor):
         self._flat_fast = visible and not self._hook_addons
         # camera images live in their own buffers, not in the observation rows: with a camera the flat observation is
         # assembled by flatten() (reference utils.py:46-60), images included, instead of being handed out as a view
-        self._flat_obs_fast = self._flat_fast and not self.builder.cameras
+        # (likewise a lidar's scan: `own_buffers`)
+        self._flat_obs_fast = self._flat_fast and not self.builder.cameras and not any(
+            getattr(a, 'own_buffers', False) for r in self.receptors.values() for a in r.addons.values())
         if self.auto_reset and self._has_hook_terminals:
             raise ValueError('auto_reset needs every terminal addon compiled into the step kernel')
 

@@ -130,6 +130,33 @@ int32_t dg_world_render(dg_world* w, const float* state, int32_t camera, float* 
  * The environment variables DG_RENDER_NO_CULL / DG_RENDER_DIAG give the initial value, read once at dg_world_create. */
 int32_t dg_world_set_render_diag(dg_world* w, int32_t flags);
 
+/* Replaces p.rayTest / p.rayTestBatch (pybullet's batched world query; the reference itself never calls either -- no
+ * addon of its own casts rays -- so there is no call site to name: this is the query a pybullet user expects, and what
+ * the `lidar` addon is built on).  `n_rays` segments from `ray_from` to `ray_to` against the collision geometry of every
+ * env, one launch for all envs:
+ *   - the nearest ENTRY point with 0 <= frac < 1 wins;
+ *   - a ray that starts inside a convex shape does not hit that shape (only entries are reported);
+ *   - a zero-length ray hits nothing;
+ *   - ties between coincident surfaces go to the lower shape index (as in dg_world_render).
+ * dg_world_raycast_scratch_floats: floats of caller-owned device scratch dg_world_raycast needs for this world (the
+ * per-env shape pose table + the mounting frame's pose).  Like every entry after dg_world_create, neither allocates,
+ * frees nor synchronises.  DG_ERR_ARG (nothing launched, outputs untouched) for n_rays <= 0, NULL frac, NULL scratch,
+ * and body, frame or skip_body out of range. */
+int64_t dg_world_raycast_scratch_floats(const dg_world* w);
+int32_t dg_world_raycast(dg_world* w, const float* state,
+                         int32_t body, int32_t frame,        /* body -1: rays given in world coordinates; else in the URDF link frame
+                                                                `frame` (pybullet joint index, -1 = base: the pose pybullet reports
+                                                                for the base, as for a camera) of `body`, per env */
+                         int32_t n_rays, const float* ray_from, const float* ray_to,
+                         int32_t per_env,                    /* 0: [n_rays][3] shared by all envs; 1: [num_envs][n_rays][3] */
+                         int32_t skip_body,                  /* -1, or a body whose shapes no ray can hit (the sensor's own model) */
+                         float* scratch,
+                         float* frac,      /* [num_envs][n_rays]  hit fraction in [0,1): hit = from + frac (to - from); 1.0 = nothing hit */
+                         int32_t* id,      /* [num_envs][n_rays]  uid + ((link + 1) << 24) exactly as dg_world_render's seg; -1 = nothing hit; may be NULL */
+                         float* pos,       /* [num_envs][n_rays][3] world hit position (world `to` on a miss); may be NULL */
+                         float* normal,    /* [num_envs][n_rays][3] world unit normal at the hit (0 on a miss); may be NULL */
+                         void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
