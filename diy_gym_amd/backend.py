@@ -42,6 +42,11 @@ SYMBOLS = {
     'dg_world_raycast_scratch_floats': (ctypes.c_int64, [_vp]),
     'dg_world_raycast': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp,
                                           _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_joint_state': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
+    'dg_world_jacobian': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, _vp]),
+    'dg_world_inverse_dynamics': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_mass_matrix': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
+    'dg_world_apply_joint_torque': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp]),
     'dg_world_set_render_diag': (ctypes.c_int32, [_vp, ctypes.c_int32]),
     'dg_world_set_diag_buffer': (ctypes.c_int32, [_vp, _vp]),
     'dg_world_set_profile_buffer': (ctypes.c_int32, [_vp, _vp]),
@@ -142,6 +147,7 @@ class HipBackend:
             self.rew_sum = torch.zeros((B, ), dtype=torch.float32, device=dev)
             self.term_flag = torch.zeros((B, ), dtype=torch.uint8, device=dev)
         self._ray_scratch, self._ray_out = None, {}   # ray_test_batch: the pose scratch and the output buffers per `want`
+        self._dyn_out = {}   # the dynamics queries' output buffers per (call kind, body)
         self._check(self.lib.dg_world_init_state(self.handle, _ptr(self.state), self._stream()))
 
     def _stream(self):
@@ -316,6 +322,94 @@ class HipBackend:
                                               int(skip_body), _ptr(self._ray_scratch), _ptr(out.frac), _ptr(out.id), _ptr(out.pos), _ptr(out.normal),
                                               self._stream()))
         return out
+
+    # -- batched p.getJointStates / p.calculateJacobian / p.calculateInverseDynamics / p.calculateMassMatrix / TORQUE_CONTROL ----
+    # For addons written in Python (an operational-space or computed-torque controller ported from pybullet; reference
+    # diy_gym/addons/controllers/admittance_controller.py:36-55).  Fixed-base bodies with at least one joint only: anything else
+    # raises ValueError.  ``body`` is a Model's ``uid``; the uid of a child model merged into its parent is an alias of the
+    # PARENT's body, so ``nv`` -- the number of joints, the width of every vector below -- is then the parent's, in the order of
+    # the merged body's joints.  Vectors are float32 ``[B, nv]`` on this device (or one ``[nv]`` vector for every env).  Outputs
+    # are buffers kept per call kind and body and REUSED by the next call of that kind: clone what must last.
+    def _dyn_check(self, rc):
+        if rc == -4:   # DG_ERR_ARG: a body or frame the queries do not take
+            raise ValueError(self.lib.dg_last_error().decode())
+        self._check(rc)
+
+    def _dyn_body(self, body, frame=-1):
+        """``(body index, body-local frame, nv)``; ValueError for a body the dynamics queries do not take."""
+        body, frame = self.layout.resolve_frame(body, frame)
+        if not 0 <= body < self.layout.n_bodies:
+            raise ValueError('body %d out of range' % body)
+        nv = int(self.layout.body_n_links[body])
+        if not self.layout.body_fixed[body] or nv < 1:
+            raise ValueError('body %d is not a fixed-base body with joints: the dynamics queries take no other' % body)
+        return body, frame, nv
+
+    def _rows_nv(self, name, v, nv):
+        """``v`` (float32, this device) as a contiguous ``[num_envs, nv]`` tensor: one ``[nv]`` vector for every env, or one per env."""
+        if v is None:
+            return None
+        if isinstance(v, torch.Tensor) and v.dim() == 1:   # broadcast into a buffer kept per argument: no allocation per call
+            buf = self._dyn_buf('in_' + name, nv, self.num_envs, nv)
+            buf.copy_(self._require(name, v, (nv, ), torch.float32).reshape(1, nv))
+            return buf
+        return self._require(name, v, (self.num_envs, nv), torch.float32)
+
+    def _dyn_buf(self, kind, body, *shape):
+        key = (kind, body)
+        if key not in self._dyn_out:
+            self._dyn_out[key] = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        return self._dyn_out[key]
+
+    def joint_states(self, body):
+        """``p.getJointStates`` (positions and velocities) for every env: ``(q, qd)``, each ``[B, nv]``."""
+        body, _, nv = self._dyn_body(body)
+        q, qd = self._dyn_buf('q', body, self.num_envs, nv), self._dyn_buf('qd', body, self.num_envs, nv)
+        self._dyn_check(self.lib.dg_world_joint_state(self.handle, _ptr(self.state), body, _ptr(q), _ptr(qd), self._stream()))
+        return q, qd
+
+    def calculate_jacobian(self, body, frame, local_pos=(0.0, 0.0, 0.0), q=None):
+        """``p.calculateJacobian(uid, linkIndex, localPosition, q, ...)`` for every env: ``(jac_t, jac_r)``, each ``[B, 3, nv]`` in
+        world coordinates.  ``frame`` is the index ``Model.get_frame_id`` returns (>= 0), ``local_pos`` three numbers in the
+        link's INERTIAL frame, ``q`` the joint positions to evaluate at (default: each env's current ones).  When ``body`` is a
+        merged child's alias the frame lands on the parent's body and ``nv`` is the parent's."""
+        if int(frame) < 0:
+            raise ValueError('frame must be a frame id >= 0, got %d' % int(frame))
+        body, frame, nv = self._dyn_body(body, frame)
+        lp = np.asarray(local_pos, dtype=np.float32).reshape(-1)
+        if lp.size != 3:
+            raise ValueError('local_pos must have 3 elements, got %d' % lp.size)
+        q = self._rows_nv('q', q, nv)
+        jt, jr = self._dyn_buf('jac_t', body, self.num_envs, 3, nv), self._dyn_buf('jac_r', body, self.num_envs, 3, nv)
+        self._dyn_check(self.lib.dg_world_jacobian(self.handle, _ptr(self.state), body, frame, (ctypes.c_float * 3)(*lp.tolist()), _ptr(q), _ptr(jt), _ptr(jr),
+                                                   self._stream()))
+        return jt, jr
+
+    def calculate_inverse_dynamics(self, body, q=None, qd=None, qdd=None):
+        """``p.calculateInverseDynamics(uid, q, qd, qdd)`` for every env: ``[B, nv]`` joint torques ``M qdd + C qd - G`` (rigid-body
+        terms only).  ``q`` / ``qd`` default to each env's current values, ``qdd`` to zero; with ``qd`` and ``qdd`` zero the
+        result is the gravity compensation."""
+        body, _, nv = self._dyn_body(body)
+        q, qd, qdd = self._rows_nv('q', q, nv), self._rows_nv('qd', qd, nv), self._rows_nv('qdd', qdd, nv)
+        tau = self._dyn_buf('tau', body, self.num_envs, nv)
+        self._dyn_check(self.lib.dg_world_inverse_dynamics(self.handle, _ptr(self.state), body, _ptr(q), _ptr(qd), _ptr(qdd), _ptr(tau), self._stream()))
+        return tau
+
+    def calculate_mass_matrix(self, body, q=None):
+        """``p.calculateMassMatrix(uid, q)`` for every env: ``[B, nv, nv]``, symmetric bit for bit."""
+        body, _, nv = self._dyn_body(body)
+        q = self._rows_nv('q', q, nv)
+        M = self._dyn_buf('M', body, self.num_envs, nv, nv)
+        self._dyn_check(self.lib.dg_world_mass_matrix(self.handle, _ptr(self.state), body, _ptr(q), _ptr(M), self._stream()))
+        return M
+
+    def apply_joint_torque(self, body, torque):
+        """``p.setJointMotorControlArray(uid, joints, p.TORQUE_CONTROL, forces=torque)`` for every env: ``torque`` (``[B, nv]`` or
+        ``[nv]``) is ADDED to the joints' torques for the next ``step`` only, on top of what compiled addons apply."""
+        body, _, nv = self._dyn_body(body)
+        if torque is None:
+            raise ValueError('torque must be a torch.Tensor, got None')
+        self._dyn_check(self.lib.dg_world_apply_joint_torque(self.handle, _ptr(self.state), body, _ptr(self._rows_nv('torque', torque, nv)), self._stream()))
 
     def set_render_diag(self, flags):
         """Diagnostic switches of ``render`` (1: no culling -- the brute-force picture; see dg_world_set_render_diag)."""

@@ -17,6 +17,7 @@
 #define DG_DEFINE_RENDER_KERNEL
 #include "dg_render.h"
 #include "dg_raycast.h"
+#include "dg_dynq.h"
 
 using namespace dg;
 
@@ -195,6 +196,14 @@ int32_t dg_world_init_state(dg_world* w, float* state, void* stream) {
   return DG_OK;
 }
 
+// `frame` as the C-ABI takes it -- the body-local pybullet joint index -- to the global frame index the kernels use; -1: the body
+// has no such frame
+static int global_frame(const dg_world* w, int32_t body, int32_t frame) {
+  const int32_t* I = w->I.data(); const int32_t* FI = I + I[DG_H_OFF_FRAME_I]; int seen = 0;
+  for (int f = 0; f < w->sc.nfr; f++) if (FI[f * DG_FI_STRIDE + DG_FI_BODY] == body) { if (seen == frame) return f; seen++; }
+  return -1;
+}
+
 static dim3 grid_of(const dg_world* w) { const int per = envs_per_wave(w->lanes); return dim3((w->num_envs + per - 1) / per); }
 
 int32_t dg_world_reset(dg_world* w, float* state, const uint8_t* mask, float* obs, void* stream) {
@@ -296,11 +305,7 @@ int32_t dg_world_raycast(dg_world* w, const float* state, int32_t body, int32_t 
   if (body < 0 && frame != -1) return fail(DG_ERR_ARG, "frame %d given without a body", frame);
   if (frame < -1) return fail(DG_ERR_ARG, "frame %d out of range", frame);
   int gf = -1;  // `frame` is the body-local pybullet joint index; the kernels use the global frame index
-  if (frame >= 0) {
-    const int32_t* I = w->I.data(); const int32_t* FI = I + I[DG_H_OFF_FRAME_I]; int seen = 0; bool found = false;
-    for (int f = 0; f < w->sc.nfr; f++) if (FI[f * DG_FI_STRIDE + DG_FI_BODY] == body) { if (seen == frame) { gf = f; found = true; break; } seen++; }
-    if (!found) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
-  }
+  if (frame >= 0 && (gf = global_frame(w, body, frame)) < 0) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
   // one workgroup per (env, chunk of rays): a wavefront per 64 rays, at most four of them
   const int threads = 64 * std::min(4, (n_rays + 63) / 64), nchunks = (n_rays + threads - 1) / threads;
   const long long blocks = (long long)nchunks * w->num_envs;  // the env index is folded into grid.x
@@ -446,13 +451,8 @@ int32_t dg_world_observe(dg_world* w, const float* state, float* obs, float* rew
 int32_t dg_world_frame_state(dg_world* w, const float* state, int32_t body, int32_t frame, int32_t com, float* out, void* stream) {
   if (!w || !state || !out) return fail(DG_ERR_ARG, "null argument");
   if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "body %d out of range", body);
-  // `frame` is the body-local pybullet joint index; the kernels use the global frame index
-  int gf = -1;
-  if (frame >= 0) {
-    const int32_t* I = w->I.data(); const int32_t* FI = I + I[DG_H_OFF_FRAME_I]; int seen = 0; bool found = false;
-    for (int f = 0; f < w->sc.nfr; f++) if (FI[f * DG_FI_STRIDE + DG_FI_BODY] == body) { if (seen == frame) { gf = f; found = true; break; } seen++; }
-    if (!found) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
-  }
+  int gf = -1;  // `frame` is the body-local pybullet joint index; the kernels use the global frame index
+  if (frame >= 0 && (gf = global_frame(w, body, frame)) < 0) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
   DG_ON_DEVICE(w->device);
   launch_table(w->lanes, w->mf).frame(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, gf, com, out, w->d_gws);
   HIP_TRY(hipGetLastError());
@@ -473,14 +473,73 @@ int32_t dg_world_apply_wrench(dg_world* w, float* state, int32_t body, int32_t f
   if (I[I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE + DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "body %d is part of the frozen static world: it has no state to push on", body);
   if (flags != DG_WRENCH_WORLD_FRAME && flags != DG_WRENCH_LINK_FRAME) return fail(DG_ERR_ARG, "flags must be DG_WRENCH_LINK_FRAME (1) or DG_WRENCH_WORLD_FRAME (2)");
   int gf = -1;  // `frame` is the body-local pybullet joint index; the kernels use the global frame index
-  if (frame >= 0) {
-    const int32_t* FI = I + I[DG_H_OFF_FRAME_I]; int seen = 0; bool found = false;
-    for (int f = 0; f < w->sc.nfr; f++) if (FI[f * DG_FI_STRIDE + DG_FI_BODY] == body) { if (seen == frame) { gf = f; found = true; break; } seen++; }
-    if (!found) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
-  }
+  if (frame >= 0 && (gf = global_frame(w, body, frame)) < 0) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
   if (!force && !torque) return DG_OK;
   DG_ON_DEVICE(w->device);
   launch_table(w->lanes, w->mf).wrench(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, gf, flags == DG_WRENCH_LINK_FRAME ? 1 : 0, force, pos, torque, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// ------------------------------------------------------------------ dynamics queries (dg_dynq.h)
+// the checks the five entries share: a fixed-base body with joints whose passes fit the transient region; 0 or the error code
+static int dynq_check(const dg_world* w, const void* state, int32_t body, int kind, const char* what) {
+  if (!w || !state) return fail(DG_ERR_ARG, "%s: null argument", what);
+  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "%s: body %d out of range", what, body);
+  const int32_t* I = w->I.data(); const int32_t* B = I + I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE;
+  if (B[DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "%s: body %d is part of the frozen static world: it has no joints", what, body);
+  if (!(B[DG_BI_FLAGS] & DG_BODY_FIXED)) return fail(DG_ERR_ARG, "%s: body %d has a floating base; the dynamics queries take fixed-base bodies only", what, body);
+  if (B[DG_BI_N_LINKS] < 1) return fail(DG_ERR_ARG, "%s: body %d has no joints", what, body);
+  if (kind >= 0 && dynq_slots(kind, B[DG_BI_N_LINKS]) > w->sc.tr_slots)
+    return fail(DG_ERR_ARG, "%s: body %d needs %d workspace slots, the world's transient region has %d", what, body, dynq_slots(kind, B[DG_BI_N_LINKS]), w->sc.tr_slots);
+  return DG_OK;
+}
+
+int32_t dg_world_joint_state(dg_world* w, const float* state, int32_t body, float* q_out, float* qd_out, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_joint_state")) return rc;
+  if (!q_out && !qd_out) return DG_OK;
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).joint_state(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, q_out, qd_out, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+int32_t dg_world_jacobian(dg_world* w, const float* state, int32_t body, int32_t frame, const float* local_pos, const float* q, float* jac_t, float* jac_r, void* stream) {
+  if (const int rc = dynq_check(w, state, body, DQ_KIND_JACOBIAN, "dg_world_jacobian")) return rc;
+  if (!local_pos) return fail(DG_ERR_ARG, "dg_world_jacobian: local_pos is NULL (three host floats)");
+  if (frame < 0) return fail(DG_ERR_ARG, "dg_world_jacobian: frame %d out of range (the base of a fixed body does not move)", frame);
+  const int gf = global_frame(w, body, frame);
+  if (gf < 0) return fail(DG_ERR_ARG, "dg_world_jacobian: body %d has no frame %d", body, frame);
+  if (!jac_t && !jac_r) return DG_OK;
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).jacobian(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, gf, local_pos[0], local_pos[1], local_pos[2], q, jac_t, jac_r, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+int32_t dg_world_inverse_dynamics(dg_world* w, const float* state, int32_t body, const float* q, const float* qd, const float* qdd, float* tau, void* stream) {
+  if (const int rc = dynq_check(w, state, body, DQ_KIND_ID, "dg_world_inverse_dynamics")) return rc;
+  if (!tau) return fail(DG_ERR_ARG, "dg_world_inverse_dynamics: tau is NULL");
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).inverse_dynamics(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, q, qd, qdd, tau, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+int32_t dg_world_mass_matrix(dg_world* w, const float* state, int32_t body, const float* q, float* M, void* stream) {
+  if (const int rc = dynq_check(w, state, body, DQ_KIND_MASS, "dg_world_mass_matrix")) return rc;
+  if (!M) return fail(DG_ERR_ARG, "dg_world_mass_matrix: M is NULL");
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).mass_matrix(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, q, M, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+int32_t dg_world_apply_joint_torque(dg_world* w, float* state, int32_t body, const float* tau, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_apply_joint_torque")) return rc;
+  if (!tau) return fail(DG_ERR_ARG, "dg_world_apply_joint_torque: tau is NULL");
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).joint_torque(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, tau, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }

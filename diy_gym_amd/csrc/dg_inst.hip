@@ -1,6 +1,6 @@
 // dg_inst.hip -- instantiates the kernels of one envs-per-wavefront mode.  Compiled several times:
 //   -DDG_LANES={64,32,16,8,4,1,0}  -DDG_PART=0  step kernels (+ stamped build for 64, 16 and 8)
-//                            -DDG_PART=1  reset / observe / frame / pose kernels and the mode's launch table
+//                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query kernels and the mode's launch table
 //   -DDG_LANES=64            -DDG_PART=2  helper-wave step kernels
 //   -DDG_LANES=-16 -DDG_TAG=g16           the global-workspace mode with 16 envs per wavefront
 //   -DDG_MANIFOLD (with any of the above but the helper-wave part): the same kernels with the hull-hull contact manifold compiled
@@ -11,6 +11,7 @@
 #endif
 #include "dg_launch.h"
 #include "dg_entry.h"
+#include "dg_dynq.h"
 
 #define DG_CAT_(a, b) a##b
 #define DG_CAT(a, b) DG_CAT_(a, b)
@@ -69,6 +70,21 @@ static void l_wrench(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable
 static void l_pose(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int ncam, cip CI, cfp CF, float* table, float* gws, int nmount, int mbody, int mframe) {
   hipLaunchKernelGGL(pose_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, ncam, CI, CF, table, gws, nmount, mbody, mframe);
 }
+static void l_joint_state(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, float* q_out, float* qd_out, float* gws) {
+  hipLaunchKernelGGL(joint_state_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, q_out, qd_out, gws);
+}
+static void l_joint_torque(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* tau, float* gws) {
+  hipLaunchKernelGGL(joint_torque_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, tau, gws);
+}
+static void l_jacobian(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, float lx, float ly, float lz, const float* q, float* jac_t, float* jac_r, float* gws) {
+  hipLaunchKernelGGL(jacobian_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, frame, lx, ly, lz, q, jac_t, jac_r, gws);
+}
+static void l_inverse_dynamics(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* q, const float* qd, const float* qdd, float* tau, float* gws) {
+  hipLaunchKernelGGL(inverse_dynamics_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, q, qd, qdd, tau, gws);
+}
+static void l_mass_matrix(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* q, float* M, float* gws) {
+  hipLaunchKernelGGL(mass_matrix_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, q, M, gws);
+}
 static hipError_t l_prepare(int lds) {
   if (L == 0) return hipSuccess;
   if (L < 0) {  // only the step kernel uses LDS (the sliced sweeps' accumulated impulses)
@@ -77,6 +93,7 @@ static hipError_t l_prepare(int lds) {
   hipError_t e = DGL(l_prepare_step)(lds);
 #define DG_ATTR(K) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
   DG_ATTR(reset_kernel<L>); DG_ATTR(observe_kernel<L>); DG_ATTR(frame_kernel<L>); DG_ATTR(wrench_kernel<L>); DG_ATTR(pose_kernel<L>);
+  DG_ATTR(joint_state_kernel<L>); DG_ATTR(joint_torque_kernel<L>); DG_ATTR(jacobian_kernel<L>); DG_ATTR(inverse_dynamics_kernel<L>); DG_ATTR(mass_matrix_kernel<L>);
 #undef DG_ATTR
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
   if (e == hipSuccess) e = l_prepare_par_64(lds);
@@ -91,7 +108,8 @@ extern const LaunchTable DGL(g_launch_table) = {
 #else
     nullptr,
 #endif
-    l_reset, l_observe, l_frame, l_wrench, l_pose};
+    l_reset, l_observe, l_frame, l_wrench, l_pose,
+    l_joint_state, l_joint_torque, l_jacobian, l_inverse_dynamics, l_mass_matrix};
 #endif
 #endif
 

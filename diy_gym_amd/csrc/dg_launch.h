@@ -17,6 +17,12 @@ struct LaunchTable {
   void (*frame)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, int com, float* out, float* gws);
   void (*wrench)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, int link_frame, const float* force, const float* pos, const float* torque, float* gws);
   void (*pose)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int ncam, cip CI, cfp CF, float* table, float* gws, int nmount, int mbody, int mframe);
+  // dynamics queries (dg_dynq.h)
+  void (*joint_state)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, float* q_out, float* qd_out, float* gws);
+  void (*joint_torque)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* tau, float* gws);
+  void (*jacobian)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, float lx, float ly, float lz, const float* q, float* jac_t, float* jac_r, float* gws);
+  void (*inverse_dynamics)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* q, const float* qd, const float* qdd, float* tau, float* gws);
+  void (*mass_matrix)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* q, float* M, float* gws);
 };
 const LaunchTable& launch_table(int lanes);  // lanes in {64, 32, 16, 8, 4, 1, 0, -16}
 

@@ -157,6 +157,39 @@ int32_t dg_world_raycast(dg_world* w, const float* state,
                          float* normal,    /* [num_envs][n_rays][3] world unit normal at the hit (0 on a miss); may be NULL */
                          void* stream);
 
+/* Dynamics queries on a FIXED-BASE articulated body with at least one joint (DG_BODY_FIXED, not frozen): the calls an
+ * operational-space, impedance or computed-torque controller written against pybullet makes (reference
+ * diy_gym/addons/controllers/admittance_controller.py:36-55), every env at once.  `nv` is the body's number of joints;
+ * columns and entries are in the order of the body's links (the URDF's movable joints, q_index order).  All arrays are device
+ * float32.  Like every entry after dg_world_create, none allocates, frees or synchronises; each is one launch on `stream`.
+ * DG_ERR_ARG (nothing launched, outputs untouched) for a NULL world or state, a body that is out of range, floating, frozen or
+ * without joints, a frame the body does not have, and a body whose passes would need more workspace than the world has.
+ *
+ * dg_world_joint_state       p.getJointStates (position and velocity): q_out, qd_out [num_envs][nv], either may be NULL.
+ * dg_world_jacobian          p.calculateJacobian: `frame` is the pybullet joint index of the link (>= 0; a frame on a fixed joint
+ *                            stands for the link it is rigidly attached to), local_pos[3] (HOST floats) a point in that link's
+ *                            INERTIAL frame (pybullet's localPosition; the frame DG_WRENCH_LINK_FRAME means).  q [num_envs][nv]
+ *                            or NULL = the env's current joint positions.  jac_t, jac_r [num_envs][3][nv] in world coordinates,
+ *                            either may be NULL; the columns of joints that are not ancestors of the link are zero.
+ * dg_world_inverse_dynamics  p.calculateInverseDynamics: tau [num_envs][nv] = M(q) qdd + C(q, qd) qd - G(q) by one recursive
+ *                            Newton-Euler pass.  q, qd [num_envs][nv] or NULL = the env's current values; qdd NULL = zero (with
+ *                            qd = qdd = 0: the torques that hold the body against gravity).  Rigid-body terms only: no joint
+ *                            damping, friction, motors or limits.
+ * dg_world_mass_matrix       p.calculateMassMatrix: M [num_envs][nv][nv] by composite rigid bodies; M[i][j] and M[j][i] are the
+ *                            same bits.
+ * dg_world_apply_joint_torque  p.setJointMotorControlArray(..., TORQUE_CONTROL, forces=tau): tau [num_envs][nv] is ADDED to
+ *                            the joints' torque slots (DG_LS_TORQUE).  It acts during the NEXT dg_world_step only and adds to
+ *                            what compiled ops apply -- the contract of dg_world_apply_wrench.
+ * Masses and inertias carry the env's mass scale (dynamics_randomizer), gravity is the scene's: these are queries on the
+ * world's state, not on the URDF. */
+int32_t dg_world_joint_state(dg_world* w, const float* state, int32_t body, float* q_out, float* qd_out, void* stream);
+int32_t dg_world_jacobian(dg_world* w, const float* state, int32_t body, int32_t frame, const float* local_pos, const float* q,
+                          float* jac_t, float* jac_r, void* stream);
+int32_t dg_world_inverse_dynamics(dg_world* w, const float* state, int32_t body, const float* q, const float* qd, const float* qdd,
+                                  float* tau, void* stream);
+int32_t dg_world_mass_matrix(dg_world* w, const float* state, int32_t body, const float* q, float* M, void* stream);
+int32_t dg_world_apply_joint_torque(dg_world* w, float* state, int32_t body, const float* tau, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
