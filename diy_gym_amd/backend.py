@@ -47,6 +47,9 @@ SYMBOLS = {
     'dg_world_inverse_dynamics': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_mass_matrix': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
     'dg_world_apply_joint_torque': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp]),
+    'dg_world_inverse_kinematics': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_set_joint_targets': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_uint64, _vp, _vp, _vp]),
+    'dg_world_reset_joint_state': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     'dg_world_set_render_diag': (ctypes.c_int32, [_vp, ctypes.c_int32]),
     'dg_world_set_diag_buffer': (ctypes.c_int32, [_vp, _vp]),
     'dg_world_set_profile_buffer': (ctypes.c_int32, [_vp, _vp]),
@@ -148,6 +151,7 @@ class HipBackend:
             self.term_flag = torch.zeros((B, ), dtype=torch.uint8, device=dev)
         self._ray_scratch, self._ray_out = None, {}   # ray_test_batch: the pose scratch and the output buffers per `want`
         self._dyn_out = {}   # the dynamics queries' output buffers per (call kind, body)
+        self._ik_list_cache = {}   # calculate_inverse_kinematics: the null-space lists on the device, per distinct value
         self._check(self.lib.dg_world_init_state(self.handle, _ptr(self.state), self._stream()))
 
     def _stream(self):
@@ -192,10 +196,8 @@ class HipBackend:
                              (name, dtype, numel, self.device, t.dtype, tuple(t.shape), t.device))
         return t
 
-    # -- step path --------------------------------------------------------
-    def reset(self, mask=None):
-        """``mask``: None (all envs) or one flag per env; bool / uint8 masks on the backend's device are used as they
-        are (a bool tensor is reinterpreted, not copied), anything else is converted."""
+    def _env_mask(self, mask):
+        """``mask`` (None, or one flag per env) as None or a contiguous uint8 tensor on this device."""
         if mask is not None:
             if not isinstance(mask, torch.Tensor):
                 mask = torch.as_tensor(mask)
@@ -205,6 +207,13 @@ class HipBackend:
                 mask = mask.view(torch.uint8)
             elif mask.dtype != torch.uint8 or mask.device != self.device or not mask.is_contiguous():
                 mask = (mask != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        return mask
+
+    # -- step path --------------------------------------------------------
+    def reset(self, mask=None):
+        """``mask``: None (all envs) or one flag per env; bool / uint8 masks on the backend's device are used as they
+        are (a bool tensor is reinterpreted, not copied), anything else is converted."""
+        mask = self._env_mask(mask)
         self._check(self.lib.dg_world_reset(self.handle, _ptr(self.state), _ptr(mask), _ptr(self.obs), self._stream()))
 
     def step(self, update_mask, actions=None):
@@ -410,6 +419,104 @@ class HipBackend:
         if torque is None:
             raise ValueError('torque must be a torch.Tensor, got None')
         self._dyn_check(self.lib.dg_world_apply_joint_torque(self.handle, _ptr(self.state), body, _ptr(self._rows_nv('torque', torque, nv)), self._stream()))
+
+    # -- batched p.calculateInverseKinematics / POSITION_CONTROL, VELOCITY_CONTROL targets / p.resetJointState ----------------
+    # The position-level half of the same contract (reference diy_gym/addons/controllers/ik_controller.py:47-80): same bodies,
+    # same conventions, same reused output buffers as the dynamics queries above.
+    def _ik_lists(self, nv, rest, lower, upper, ranges):
+        """The four null-space lists as one device ``[4, nv]`` tensor in the order rest, lower, upper, range -- uploaded once per
+        distinct value and kept; None when none is given.  ValueError for a partial set or a list of another length."""
+        given = [v is not None for v in (rest, lower, upper, ranges)]
+        if not any(given):
+            return None
+        if not all(given):
+            raise ValueError('the null-space term takes all four of lower, upper, ranges, rest; got only %s' %
+                             ', '.join(n for n, g in zip(('rest', 'lower', 'upper', 'ranges'), given) if g))
+        rows = []
+        for name, v in (('rest', rest), ('lower', lower), ('upper', upper), ('ranges', ranges)):
+            row = tuple(float(x) for x in (v.tolist() if hasattr(v, 'tolist') else v))
+            if len(row) != nv:
+                raise ValueError('%s must have %d entries (one per joint of the body), got %d' % (name, nv, len(row)))
+            rows.append(row)
+        key = tuple(rows)
+        if key not in self._ik_list_cache:
+            self._ik_list_cache[key] = torch.tensor(rows, dtype=torch.float32, device=self.device)
+        return self._ik_list_cache[key]
+
+    def _joint_mask(self, joints, nv):
+        """The bit mask of ``joints`` (indices of the body's joints; None: all of them)."""
+        if joints is None:
+            return ctypes.c_uint64(0xFFFFFFFFFFFFFFFF)
+        m = 0
+        for j in joints:
+            if not 0 <= int(j) < min(nv, 64):
+                raise ValueError('joint %d out of range (the body has %d joints; a joint list reaches the first 64)' % (int(j), nv))
+            m |= 1 << int(j)
+        return ctypes.c_uint64(m)
+
+    def calculate_inverse_kinematics(self, body, frame, target_pos, target_orn=None, lower=None, upper=None, ranges=None, rest=None, q0=None,
+                                     return_iters=False):
+        """``p.calculateInverseKinematics(uid, linkIndex, targetPosition, targetOrientation, lowerLimits, upperLimits, jointRanges,
+        restPoses)`` for every env: ``[B, nv]`` joint positions, or ``(q, iters)`` with ``return_iters`` (``iters``: int32 ``[B]``,
+        the iterations each env ran before its position error fell below the world's ``ik_residual``).  The recursion, its
+        iteration count, damping, clamp and gains are those of the world's ``ik_controller`` op (the engine parameters ``ik_*``).
+        ``frame`` is the index ``Model.get_frame_id`` returns (>= 0); the target is the pose of that link's INERTIAL frame -- what
+        ``frame_state(uid, frame, com=True)`` reports -- as ``[B, 3]`` (or one 3-vector) and a unit quaternion xyzw ``[B, 4]`` (or one;
+        None: position only).  ``lower, upper, ranges, rest``: host sequences of ``nv`` numbers; the null-space term is on when all
+        four are given, a partial set raises ValueError.  ``q0``: where the iteration starts (default: each env's current joint
+        positions).  The state is not written."""
+        if int(frame) < 0:
+            raise ValueError('frame must be a frame id >= 0, got %d' % int(frame))
+        body, frame, nv = self._dyn_body(body, frame)
+        lists = self._ik_lists(nv, rest, lower, upper, ranges)
+        tp = self._rows_k('target_pos', target_pos, 3, body)
+        if tp is None:
+            raise ValueError('target_pos must be a torch.Tensor, got None')
+        to = self._rows_k('target_orn', target_orn, 4, body)
+        q0 = self._rows_nv('q0', q0, nv)
+        q = self._dyn_buf('ik_q', body, self.num_envs, nv)
+        key = ('ik_iters', body)
+        if return_iters and key not in self._dyn_out:
+            self._dyn_out[key] = torch.zeros((self.num_envs, ), dtype=torch.int32, device=self.device)
+        it = self._dyn_out[key] if return_iters else None
+        self._dyn_check(self.lib.dg_world_inverse_kinematics(self.handle, _ptr(self.state), body, frame, _ptr(tp), _ptr(to), _ptr(lists), _ptr(q0), _ptr(q),
+                                                             _ptr(it), self._stream()))
+        return (q, it) if return_iters else q
+
+    def _rows_k(self, name, v, k, body):
+        """``v`` (float32, this device) as a contiguous ``[num_envs, k]`` tensor: one ``[k]`` vector for every env, or one per env."""
+        if v is None:
+            return None
+        if isinstance(v, torch.Tensor) and v.dim() == 1:
+            buf = self._dyn_buf('in_' + name, body, self.num_envs, k)
+            buf.copy_(self._require(name, v, (k, ), torch.float32).reshape(1, k))
+            return buf
+        return self._require(name, v, (self.num_envs, k), torch.float32)
+
+    def set_joint_motor_targets(self, body, positions=None, velocities=None, joints=None):
+        """``p.setJointMotorControlArray(uid, joints, p.POSITION_CONTROL, targetPositions=positions[, targetVelocities=velocities])``
+        or, with ``velocities`` alone, ``(uid, joints, p.VELOCITY_CONTROL, targetVelocities=velocities)`` for every env.  Both are
+        ``[B, nv]`` (or ``[nv]``) over ALL the body's joints; ``joints`` (indices of the body's joints, default all) selects the
+        columns that are written.  The position form sets the velocity target to ``velocities`` or 0, the velocity form sets the
+        position target to 0.  Targets persist until overwritten; gains and force limits are the motor table's (``set_motor_cfg``)."""
+        body, _, nv = self._dyn_body(body)
+        if positions is None and velocities is None:
+            raise ValueError('give positions, velocities or both')
+        pos, vel = self._rows_nv('positions', positions, nv), self._rows_nv('velocities', velocities, nv)
+        self._dyn_check(self.lib.dg_world_set_joint_targets(self.handle, _ptr(self.state), body, self._joint_mask(joints, nv), _ptr(pos), _ptr(vel),
+                                                            self._stream()))
+
+    def reset_joint_state(self, body, q, qd=None, joints=None, mask=None):
+        """``p.resetJointState(uid, joint, q, qd)`` for the joints ``joints`` (default all) of the envs ``mask`` selects (as for
+        ``reset``; default all): ``q`` and ``qd`` are ``[B, nv]`` (or ``[nv]``) over ALL the body's joints, ``qd`` defaults to zero.
+        Motor targets are left alone, as in pybullet; the reset envs' contact impulse cache is emptied.  Observations are refreshed by
+        the next ``observe()`` or ``step()``."""
+        body, _, nv = self._dyn_body(body)
+        if q is None:
+            raise ValueError('q must be a torch.Tensor, got None')
+        q, qd = self._rows_nv('q', q, nv), self._rows_nv('qd', qd, nv)
+        self._dyn_check(self.lib.dg_world_reset_joint_state(self.handle, _ptr(self.state), body, self._joint_mask(joints, nv), _ptr(q), _ptr(qd),
+                                                            _ptr(self._env_mask(mask)), self._stream()))
 
     def set_render_diag(self, flags):
         """Diagnostic switches of ``render`` (1: no culling -- the brute-force picture; see dg_world_set_render_diag)."""

@@ -18,6 +18,7 @@
 #include "dg_render.h"
 #include "dg_raycast.h"
 #include "dg_dynq.h"
+#include "dg_ikq.h"
 
 using namespace dg;
 
@@ -540,6 +541,51 @@ int32_t dg_world_apply_joint_torque(dg_world* w, float* state, int32_t body, con
   if (!tau) return fail(DG_ERR_ARG, "dg_world_apply_joint_torque: tau is NULL");
   DG_ON_DEVICE(w->device);
   launch_table(w->lanes, w->mf).joint_torque(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, tau, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// ------------------------------------------------------------------ inverse-kinematics query, motor targets, joint reset (dg_ikq.h)
+int32_t dg_world_inverse_kinematics(dg_world* w, const float* state, int32_t body, int32_t frame, const float* target_pos, const float* target_orn,
+                                    const float* lists, const float* q0, float* q_out, int32_t* iters_out, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_inverse_kinematics")) return rc;
+  const int n = w->I[w->I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE + DG_BI_N_LINKS];
+  if (ikq_slots(n) > w->sc.tr_slots)
+    return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: body %d needs %d workspace slots, the world's transient region has %d", body, ikq_slots(n), w->sc.tr_slots);
+  if (frame < 0) return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: frame %d out of range (the base of a fixed body does not move)", frame);
+  const int gf = global_frame(w, body, frame);
+  if (gf < 0) return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: body %d has no frame %d", body, frame);
+  if (!target_pos) return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: target_pos is NULL");
+  if (!q_out) return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: q_out is NULL");
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).ik_query(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, gf, target_pos, target_orn, lists, q0, q_out, iters_out, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// a mask other than all ones cannot name the joints past the 64th
+static int joint_mask_check(const dg_world* w, int32_t body, uint64_t joint_mask, const char* what) {
+  const int n = w->I[w->I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE + DG_BI_N_LINKS];
+  if (n > 64 && joint_mask != ~0ull) return fail(DG_ERR_ARG, "%s: body %d has %d joints; a partial joint mask covers 64", what, body, n);
+  return DG_OK;
+}
+
+int32_t dg_world_set_joint_targets(dg_world* w, float* state, int32_t body, uint64_t joint_mask, const float* pos, const float* vel, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_set_joint_targets")) return rc;
+  if (const int rc = joint_mask_check(w, body, joint_mask, "dg_world_set_joint_targets")) return rc;
+  if (!pos && !vel) return fail(DG_ERR_ARG, "dg_world_set_joint_targets: pos and vel are both NULL");
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).joint_targets(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, joint_mask, pos, vel, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+int32_t dg_world_reset_joint_state(dg_world* w, float* state, int32_t body, uint64_t joint_mask, const float* q, const float* qd, const uint8_t* env_mask, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_reset_joint_state")) return rc;
+  if (const int rc = joint_mask_check(w, body, joint_mask, "dg_world_reset_joint_state")) return rc;
+  if (!q) return fail(DG_ERR_ARG, "dg_world_reset_joint_state: q is NULL");
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).joint_reset(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, joint_mask, q, qd, env_mask, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }

@@ -1,6 +1,6 @@
 // dg_inst.hip -- instantiates the kernels of one envs-per-wavefront mode.  Compiled several times:
 //   -DDG_LANES={64,32,16,8,4,1,0}  -DDG_PART=0  step kernels (+ stamped build for 64, 16 and 8)
-//                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query kernels and the mode's launch table
+//                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query / IK-query kernels and the mode's launch table
 //   -DDG_LANES=64            -DDG_PART=2  helper-wave step kernels
 //   -DDG_LANES=-16 -DDG_TAG=g16           the global-workspace mode with 16 envs per wavefront
 //   -DDG_MANIFOLD (with any of the above but the helper-wave part): the same kernels with the hull-hull contact manifold compiled
@@ -12,6 +12,9 @@
 #include "dg_launch.h"
 #include "dg_entry.h"
 #include "dg_dynq.h"
+#if DG_PART == 1
+#include "dg_ikq.h"
+#endif
 
 #define DG_CAT_(a, b) a##b
 #define DG_CAT(a, b) DG_CAT_(a, b)
@@ -85,6 +88,15 @@ static void l_inverse_dynamics(dim3 grid, int lds, hipStream_t st, DevScene sc, 
 static void l_mass_matrix(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* q, float* M, float* gws) {
   hipLaunchKernelGGL(mass_matrix_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, q, M, gws);
 }
+static void l_ik_query(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, const float* target_pos, const float* target_orn, const float* lists, const float* q0, float* q_out, int32_t* iters_out, float* gws) {
+  hipLaunchKernelGGL(ik_query_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, frame, target_pos, target_orn, lists, q0, q_out, iters_out, gws);
+}
+static void l_joint_targets(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, uint64_t joint_mask, const float* pos, const float* vel, float* gws) {
+  hipLaunchKernelGGL(joint_targets_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, joint_mask, pos, vel, gws);
+}
+static void l_joint_reset(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, uint64_t joint_mask, const float* q, const float* qd, const uint8_t* env_mask, float* gws) {
+  hipLaunchKernelGGL(joint_reset_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, joint_mask, q, qd, env_mask, gws);
+}
 static hipError_t l_prepare(int lds) {
   if (L == 0) return hipSuccess;
   if (L < 0) {  // only the step kernel uses LDS (the sliced sweeps' accumulated impulses)
@@ -94,6 +106,7 @@ static hipError_t l_prepare(int lds) {
 #define DG_ATTR(K) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
   DG_ATTR(reset_kernel<L>); DG_ATTR(observe_kernel<L>); DG_ATTR(frame_kernel<L>); DG_ATTR(wrench_kernel<L>); DG_ATTR(pose_kernel<L>);
   DG_ATTR(joint_state_kernel<L>); DG_ATTR(joint_torque_kernel<L>); DG_ATTR(jacobian_kernel<L>); DG_ATTR(inverse_dynamics_kernel<L>); DG_ATTR(mass_matrix_kernel<L>);
+  DG_ATTR(ik_query_kernel<L>); DG_ATTR(joint_targets_kernel<L>); DG_ATTR(joint_reset_kernel<L>);
 #undef DG_ATTR
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
   if (e == hipSuccess) e = l_prepare_par_64(lds);
@@ -109,7 +122,8 @@ extern const LaunchTable DGL(g_launch_table) = {
     nullptr,
 #endif
     l_reset, l_observe, l_frame, l_wrench, l_pose,
-    l_joint_state, l_joint_torque, l_jacobian, l_inverse_dynamics, l_mass_matrix};
+    l_joint_state, l_joint_torque, l_jacobian, l_inverse_dynamics, l_mass_matrix,
+    l_ik_query, l_joint_targets, l_joint_reset};
 #endif
 #endif
 

@@ -23,6 +23,10 @@ struct LaunchTable {
   void (*jacobian)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, float lx, float ly, float lz, const float* q, float* jac_t, float* jac_r, float* gws);
   void (*inverse_dynamics)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* q, const float* qd, const float* qdd, float* tau, float* gws);
   void (*mass_matrix)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* q, float* M, float* gws);
+  // inverse-kinematics query, motor targets, joint reset (dg_ikq.h)
+  void (*ik_query)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, const float* target_pos, const float* target_orn, const float* lists, const float* q0, float* q_out, int32_t* iters_out, float* gws);
+  void (*joint_targets)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, uint64_t joint_mask, const float* pos, const float* vel, float* gws);
+  void (*joint_reset)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, uint64_t joint_mask, const float* q, const float* qd, const uint8_t* env_mask, float* gws);
 };
 const LaunchTable& launch_table(int lanes);  // lanes in {64, 32, 16, 8, 4, 1, 0, -16}
 

@@ -208,7 +208,9 @@ class DIYGym(Receptor):
         return [seed]
 
     def reset(self, mask=None):
-        """Reference diy_gym.py:130-148 (per-env ``mask`` is an extension)."""
+        """Reference diy_gym.py:130-148 (per-env ``mask`` is an extension).  A hook addon's ``reset()`` keeps the
+        reference's signature; it finds the mask of the reset in progress -- None: every env -- in ``env.reset_mask``."""
+        self.reset_mask = mask
         for addon in self._hook_addons:
             addon.reset()
         self.sim.reset(mask)

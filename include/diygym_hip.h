@@ -190,6 +190,47 @@ int32_t dg_world_inverse_dynamics(dg_world* w, const float* state, int32_t body,
 int32_t dg_world_mass_matrix(dg_world* w, const float* state, int32_t body, const float* q, float* M, void* stream);
 int32_t dg_world_apply_joint_torque(dg_world* w, float* state, int32_t body, const float* tau, void* stream);
 
+/* Inverse-kinematics query, motor targets and joint reset: with the queries above, what a position-level controller written
+ * against pybullet calls (reference diy_gym/addons/controllers/ik_controller.py:47-80, joint_controller.py:38-53), every env at
+ * once.  Same bodies and the same rules as the dynamics queries: device float32 arrays, one launch on `stream`, nothing
+ * allocated, freed or synchronised; DG_ERR_ARG (nothing launched, outputs untouched) for a NULL world or state, a body that is
+ * out of range, floating, frozen or without joints, a frame the body does not have, a NULL required output or input, and a
+ * body whose pass would need more workspace than the world has (the query: 9 x nv slots of the transient region).
+ *
+ * dg_world_inverse_kinematics  p.calculateInverseKinematics: the recursion of the compiled DG_OP_IK_CONTROL's general solve,
+ *                            statement for statement -- damped least squares in task space, the optional null-space projection, the
+ *                            per-iteration clamp DG_HF_IK_MAX_ANGLE and the early exit on DG_HF_IK_RESIDUAL -- with the world's
+ *                            own engine parameters, for at most the world's ik_iterations.  `frame` is the pybullet joint index
+ *                            of the link (>= 0, as for dg_world_jacobian); the target is the pose of that link's INERTIAL frame
+ *                            (what pybullet targets, what dg_world_frame_state reports with com = 1); target_orn is a unit
+ *                            quaternion.  With `lists` the null-space term pulls towards `rest` and off the limits; without,
+ *                            the solve is plain damped least squares with DG_HF_IK_JOINT_DAMPING.  The state is not written.
+ * dg_world_set_joint_targets  p.setJointMotorControlArray with POSITION_CONTROL / VELOCITY_CONTROL targets: bit i of joint_mask
+ *                            selects joint i of the body (all ones: every joint); for those joints DG_LS_TARGET_POS and
+ *                            DG_LS_TARGET_VEL are written.  With pos: position target pos, velocity target vel or 0.  With vel
+ *                            only: velocity target vel, position target 0 -- exactly what DG_OP_JOINT_CONTROL writes.  Both
+ *                            NULL is DG_ERR_ARG.  Targets persist until overwritten (a compiled controller op on the same
+ *                            joints, when the step's update mask selects it, runs inside the step and overwrites them).  Gains
+ *                            and force limits stay in the motor table (dg_world_set_motor_cfg), uniform over envs.  A body with
+ *                            more than 64 joints takes the all-ones mask only.
+ * dg_world_reset_joint_state  p.resetJointState: DG_LS_Q and DG_LS_QD of the selected joints of the selected envs; the targets
+ *                            are left alone, as in pybullet.  The env's contact impulse cache (DG_H_WARM_OFF), where the scene
+ *                            has one, is emptied as dg_world_reset does: cached impulses of a teleported body mean nothing.
+ *                            Observations are not refreshed; the next dg_world_observe or dg_world_step does that. */
+int32_t dg_world_inverse_kinematics(dg_world* w, const float* state, int32_t body, int32_t frame,
+    const float* target_pos,   /* [num_envs][3] world position of the link's INERTIAL frame (what pybullet targets) */
+    const float* target_orn,   /* [num_envs][4] xyzw, or NULL = position only */
+    const float* lists,        /* [4][nv] rest, lower, upper, range (the order of DG_OP_IK_CONTROL's flist), uniform
+                                  over envs; NULL = no null-space term: plain damped least squares with DG_HF_IK_JOINT_DAMPING */
+    const float* q0,           /* [num_envs][nv] start, or NULL = the env's current joint positions */
+    float* q_out,              /* [num_envs][nv] */
+    int32_t* iters_out,        /* [num_envs] iterations in which the env was still live, or NULL */
+    void* stream);
+int32_t dg_world_set_joint_targets(dg_world* w, float* state, int32_t body, uint64_t joint_mask,
+    const float* pos, const float* vel /* [num_envs][nv] each, either may be NULL */, void* stream);
+int32_t dg_world_reset_joint_state(dg_world* w, float* state, int32_t body, uint64_t joint_mask,
+    const float* q, const float* qd /* [num_envs][nv]; qd NULL = zero */, const uint8_t* env_mask /* [num_envs] or NULL = all */, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
