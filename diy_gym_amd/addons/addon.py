@@ -28,11 +28,11 @@ class AddonFactory:
     class _Registry:
         def __init__(self):
             from .controllers import AdmittanceController, InverseKinematicsController, JointController, ExternalForce
-            from .sensors import Camera, ForceTorqueSensor, JointStateSensor, Lidar, ObjectStateSensor
+            from .sensors import Camera, ContactSensor, ForceTorqueSensor, JointStateSensor, Lidar, ObjectStateSensor
             from .rewards import ReachTarget, ElectricityCost, TimePenalty
             from .misc import DynamicsRandomizer, Respawn, SpawnMultiple, VisualRandomizer
             from .unsupported import StuckJointCost, DrawCoords
-            # the 17 keys of reference addon.py:36-54, and `lidar` (no counterpart there)
+            # the 17 keys of reference addon.py:36-54, and `lidar` and `contact_sensor` (no counterpart there)
             self.addons = {
                 'ik_controller': InverseKinematicsController,
                 'joint_controller': JointController,
@@ -52,6 +52,7 @@ class AddonFactory:
                 'visual_randomizer': VisualRandomizer,
                 'dynamics_randomizer': DynamicsRandomizer,
                 'lidar': Lidar,
+                'contact_sensor': ContactSensor,
             }
 
     @staticmethod

@@ -284,3 +284,71 @@ class Lidar(Addon):
         if self.use_ids:
             obs['ids'] = env._out(self._ids)
         return obs
+
+
+class ContactSensor(Addon):
+    """Touch and normal force on a model by the batched contact query (``env.sim.contact_points`` -- pybullet's
+    ``p.getContactPoints``; the reference ships no such addon).  Goes on a model.  Config keys: ``target`` (the name of another
+    model of the scene; default: contacts with any body), ``frame`` (a joint of the parent: only that link's contacts; default:
+    every link of the parent), ``terminal`` False, ``force_threshold`` 0.0 N (used with ``terminal``).
+
+    * ``touching`` ``[1]``: 1.0 when at least one matching contact has ``distance <= 0`` (the narrow phase also lists contacts
+      that are up to ``contact_margin`` apart: those do not count).
+    * ``force`` ``[1]``: the sum of the matching contacts' normal forces in newtons -- what the solver applied in the last
+      substep (``dg_world_contacts`` has the staleness rule); it needs the scene's contact impulse cache (``warmstart`` > 0).
+    * ``is_terminal()`` with ``terminal``: ``touching`` and ``force >= force_threshold``.
+
+    Evaluated by its own kernel launch (``dg_world_contacts``), lazily, the first time ``observe()`` or ``is_terminal()`` is called
+    after a step."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        from ..model import Model
+        if not isinstance(parent, Model):
+            raise ValueError('contact_sensor goes on a model, not on the environment')
+        self.uid = parent.uid
+        self.target_name = config.get('target') if 'target' in config else None
+        self.frame_id = None
+        if 'frame' in config:
+            self.frame_id = parent.get_frame_id(config.get('frame'))
+            if self.frame_id < 0:
+                raise ValueError('contact_sensor: model %r has no joint %r' % (parent.name, config.get('frame')))
+        self.terminal = bool(config.get('terminal', False))
+        self.force_threshold = float(config.get('force_threshold', 0.0))
+        box = lambda hi: spaces.Box(0., hi, shape=(1, ), dtype='float32')
+        self.observation_space = spaces.Dict(OrderedDict(touching=box(1.), force=box(np.inf)))
+        self.own_buffers = True   # like a lidar's scan, not part of the kernel's observation rows
+        self.late_terminal = self.terminal   # its terminal is evaluated after the step kernel: the env folds it into the collapsed flag
+        self.target_uid = None
+        self._tick = None
+
+    def compile(self, builder):
+        # (nothing in the scene blob: the filters are run-time arguments of dg_world_contacts; every model exists by now)
+        if self.target_name is not None:
+            models = self.env.models
+            if self.target_name not in models:
+                raise ValueError('contact_sensor: the scene has no model %r' % (self.target_name, ))
+            self.target_uid = models[self.target_name].uid
+
+    def _evaluate(self):
+        import torch
+        env = self.env
+        if self._tick != env._tick:
+            if not hasattr(env.sim, 'contact_points'):
+                raise NotImplementedError('contact_sensor needs a backend with the batched contact query (contact_points); %s has none'
+                                          % type(env.sim).__name__)
+            cp = env.sim.contact_points(self.uid, self.target_uid, self.frame_id, None, want=('distance', 'force'))
+            C = cp.distance.shape[1]
+            live = torch.arange(C, device=env.device, dtype=torch.int32)[None, :] < cp.count[:, None]
+            self._touching = (live & (cp.distance <= 0.0)).any(dim=1, keepdim=True)
+            self._force = cp.normal_force.sum(dim=1, keepdim=True)   # (the slots behind the count are 0: no mask)
+            self._tick = env._tick
+
+    def observe(self):
+        self._evaluate()
+        return OrderedDict(touching=self.env._out(self._touching.float()), force=self.env._out(self._force))
+
+    def is_terminal(self):
+        if not self.terminal:
+            return None
+        self._evaluate()
+        return self.env._out((self._touching & (self._force >= self.force_threshold))[:, 0])

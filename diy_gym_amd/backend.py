@@ -50,6 +50,7 @@ SYMBOLS = {
     'dg_world_inverse_kinematics': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_set_joint_targets': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_uint64, _vp, _vp, _vp]),
     'dg_world_reset_joint_state': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    'dg_world_contacts': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_set_render_diag': (ctypes.c_int32, [_vp, ctypes.c_int32]),
     'dg_world_set_diag_buffer': (ctypes.c_int32, [_vp, _vp]),
     'dg_world_set_profile_buffer': (ctypes.c_int32, [_vp, _vp]),
@@ -87,6 +88,10 @@ def _ptr(t):
 
 # what ray_test_batch returns: device tensors, None for the outputs `want` left out
 RayHits = collections.namedtuple('RayHits', ['frac', 'id', 'pos', 'normal'])
+
+# what contact_points returns: device tensors, None for the outputs `want` left out (count is always there)
+ContactPoints = collections.namedtuple('ContactPoints', ['count', 'id_a', 'id_b', 'pos_a', 'pos_b', 'normal', 'distance', 'normal_force'])
+CONTACT_ANY = -2   # DG_CONTACT_ANY
 
 
 def debug_plan(layout, num_envs, cu_count=256):
@@ -151,6 +156,7 @@ class HipBackend:
             self.term_flag = torch.zeros((B, ), dtype=torch.uint8, device=dev)
         self._ray_scratch, self._ray_out = None, {}   # ray_test_batch: the pose scratch and the output buffers per `want`
         self._dyn_out = {}   # the dynamics queries' output buffers per (call kind, body)
+        self._contact_out = {}   # contact_points: the output buffers per `want`
         self._ik_list_cache = {}   # calculate_inverse_kinematics: the null-space lists on the device, per distinct value
         self._check(self.lib.dg_world_init_state(self.handle, _ptr(self.state), self._stream()))
 
@@ -517,6 +523,70 @@ class HipBackend:
         q, qd = self._rows_nv('q', q, nv), self._rows_nv('qd', qd, nv)
         self._dyn_check(self.lib.dg_world_reset_joint_state(self.handle, _ptr(self.state), body, self._joint_mask(joints, nv), _ptr(q), _ptr(qd),
                                                             _ptr(self._env_mask(mask)), self._stream()))
+
+    # -- batched p.getContactPoints ---------------------------------------------------------------------------------------
+    def _contact_filter(self, side, body, link):
+        """``(body index, link index)`` of one side's filter as ``dg_world_contacts`` takes it; ValueError for what it would refuse."""
+        if body is None:
+            if link is not None:
+                raise ValueError('link_%s given without body_%s' % (side, side))
+            return CONTACT_ANY, CONTACT_ANY
+        body = int(body)
+        if body in self.layout.aliases:   # a merged child: its shapes carry the parent's uid (and their own URDF link index)
+            body = self.layout.aliases[body][0]
+        if not 0 <= body < self.layout.n_bodies:
+            raise ValueError('body_%s %d is not a model of this scene' % (side, body))
+        if link is None:
+            return body, CONTACT_ANY
+        if int(link) < -1:
+            raise ValueError('link_%s must be a frame id (-1: the base), got %d' % (side, int(link)))
+        return body, int(link)
+
+    def contact_points(self, body_a=None, body_b=None, link_a=None, link_b=None, want=('id', 'pos', 'normal', 'distance', 'force')):
+        """``p.getContactPoints(bodyA, bodyB, linkIndexA, linkIndexB)`` for every env at once.  Returns ``ContactPoints(count, id_a,
+        id_b, pos_a, pos_b, normal, distance, normal_force)`` with C = the scene's ``max_contacts``: ``count [B]`` int32, ``id_a``,
+        ``id_b`` ``[B, C]`` int32 ``uid + ((link + 1) << 24)`` (the ids of the camera's segmentation mask and of ``ray_test_batch``),
+        ``pos_a``, ``pos_b`` ``[B, C, 3]`` world points on the two surfaces, ``normal [B, C, 3]`` the unit normal on B pointing
+        towards A, ``distance [B, C]`` (negative: penetration) and ``normal_force [B, C]`` in newtons; the groups ``want`` (any of
+        'id', 'pos', 'normal', 'distance', 'force') leaves out are None.  Rows are in the order of the narrow phase's pairs; behind an
+        env's ``count`` the ids are -1 and everything else 0, so ``normal_force.sum(1)`` needs no mask.
+
+        ``body_*`` are Models' ``uid``, ``link_*`` what ``Model.get_frame_id`` returns (-1: the base); None is no filter, a link
+        without its body raises.  With ``body_a`` alone every row has that body as side A (sides swapped and the normal negated
+        where the narrow phase had it as B); with both, either orientation matches and is reported as (a, b).  The alias uid of a
+        child model merged rigidly into its parent is matched by the id the camera reports for the child's shapes: the PARENT's
+        uid, with the link index the shape has in the child's own URDF -- so an alias without a link selects the whole merged body.  A link is accepted
+        when a shape of the body carries it or the body has such a frame; a child's link index can coincide with one of the
+        parent's own, and then both match.
+
+        The geometry is that of the CURRENT state; the force is what the solver applied in the LAST substep to the contact with the
+        same key -- 0 for a contact that is new since then or whose feature changed, and for every contact after
+        ``reset_joint_state`` until the next step (``dg_world_contacts`` has the rule in full).  'force' needs the contact impulse
+        cache: a world created with ``warmstart`` and ``warmstart_friction`` both 0 raises RuntimeError when asked for it.
+
+        The tensors are views of buffers kept per ``want`` and REUSED by the next call: clone what must last."""
+        groups = ('id', 'pos', 'normal', 'distance', 'force')
+        unknown = set(want) - set(groups)
+        if unknown:
+            raise ValueError("want may name 'id', 'pos', 'normal', 'distance', 'force', got %r" % (want, ))
+        ba, la = self._contact_filter('a', body_a, link_a)
+        bb, lb = self._contact_filter('b', body_b, link_b)
+        B, C = self.num_envs, int(self.layout.max_contacts)
+        Cs = max(C, 1)   # (a scene without candidate pairs has C = 0: the buffers still exist, the views are empty)
+        need_geom = any(g in want for g in ('pos', 'normal', 'distance'))
+        key = ('id' in want, need_geom, 'force' in want)
+        if key not in self._contact_out:
+            self._contact_out[key] = (torch.zeros((B, ), dtype=torch.int32, device=self.device),
+                                      torch.empty((B, Cs, 2), dtype=torch.int32, device=self.device) if key[0] else None,
+                                      torch.empty((B, Cs, 10), dtype=torch.float32, device=self.device) if key[1] else None,
+                                      torch.empty((B, Cs), dtype=torch.float32, device=self.device) if key[2] else None)
+        count, ids, geom, force = self._contact_out[key]
+        self._dyn_check(self.lib.dg_world_contacts(self.handle, _ptr(self.state), ba, la, bb, lb, _ptr(count), _ptr(ids), _ptr(geom), _ptr(force),
+                                                   self._stream()))
+        pos, nrm, dist = 'pos' in want, 'normal' in want, 'distance' in want
+        return ContactPoints(count, None if ids is None else ids[:, :C, 0], None if ids is None else ids[:, :C, 1],
+                             geom[:, :C, 0:3] if pos else None, geom[:, :C, 3:6] if pos else None, geom[:, :C, 6:9] if nrm else None,
+                             geom[:, :C, 9] if dist else None, None if force is None else force[:, :C])
 
     def set_render_diag(self, flags):
         """Diagnostic switches of ``render`` (1: no culling -- the brute-force picture; see dg_world_set_render_diag)."""

@@ -91,7 +91,7 @@ struct dg_world {
 
 extern "C" {
 
-int32_t dg_version(void) { return (0 << 16) | 7; }
+int32_t dg_version(void) { return (0 << 16) | 8; }
 const char* dg_last_error(void) { return g_err.c_str(); }
 
 int32_t dg_world_create(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int32_t num_envs, int32_t env_stride,
@@ -586,6 +586,43 @@ int32_t dg_world_reset_joint_state(dg_world* w, float* state, int32_t body, uint
   if (!q) return fail(DG_ERR_ARG, "dg_world_reset_joint_state: q is NULL");
   DG_ON_DEVICE(w->device);
   launch_table(w->lanes, w->mf).joint_reset(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, joint_mask, q, qd, env_mask, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// ------------------------------------------------------------------ contact query (dg_contactq.h)
+// a (body, link) filter of dg_world_contacts: 0 or the error code
+static int contact_filter_check(const dg_world* w, int32_t body, int32_t link, const char* side) {
+  if (body == DG_CONTACT_ANY) {
+    if (link != DG_CONTACT_ANY) return fail(DG_ERR_ARG, "dg_world_contacts: link_%s %d given without body_%s", side, link, side);
+    return DG_OK;
+  }
+  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_contacts: body_%s %d out of range", side, body);
+  if (link == DG_CONTACT_ANY || link == -1) return DG_OK;
+  // A link the body has: one that a shape of the body carries in its id (the value the filter is compared with -- for the shapes of
+  // a rigidly merged child model that is the CHILD's own link index), or one of the body's frames (a link without collision shapes)
+  if (link >= 0) {
+    const int32_t* I = w->I.data(); const int32_t* SI = I + I[DG_H_OFF_SHAPE_I];
+    for (int s = 0; s < w->sc.nsh; s++)
+      if (SI[s * DG_SI_STRIDE + DG_SI_BODY] == body && ((SI[s * DG_SI_STRIDE + DG_SI_FLAGS] >> 8) & 0xFFFF) - 1 == link) return DG_OK;
+    if (global_frame(w, body, link) >= 0) return DG_OK;
+  }
+  return fail(DG_ERR_ARG, "dg_world_contacts: body %d has no link %d", body, link);
+}
+
+int32_t dg_world_contacts(dg_world* w, const float* state, int32_t body_a, int32_t link_a, int32_t body_b, int32_t link_b, int32_t* count, int32_t* ids,
+                          float* geom, float* force, void* stream) {
+  if (!w || !state) return fail(DG_ERR_ARG, "dg_world_contacts: null argument");
+  if (!count) return fail(DG_ERR_ARG, "dg_world_contacts: count is NULL (ids, geom and force may be)");
+  if (const int rc = contact_filter_check(w, body_a, link_a, "a")) return rc;
+  if (const int rc = contact_filter_check(w, body_b, link_b, "b")) return rc;
+  if (force && w->sc.warm_off < 0)
+    return fail(DG_ERR_UNSUPPORTED, "dg_world_contacts: the world keeps no contact impulse cache (warmstart and warmstart_friction are 0, or the scene has no "
+                                    "candidate pairs): no forces to report");
+  DG_ON_DEVICE(w->device);
+  // the grid and block of reset_kernel: one wavefront per workgroup, as many workgroups as the step has (dg_contactq.h, Workspace)
+  launch_table(w->lanes, w->mf).contacts(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body_a, link_a, body_b, link_b,
+                                         count, ids, geom, force, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }

@@ -1,6 +1,6 @@
 // dg_inst.hip -- instantiates the kernels of one envs-per-wavefront mode.  Compiled several times:
 //   -DDG_LANES={64,32,16,8,4,1,0}  -DDG_PART=0  step kernels (+ stamped build for 64, 16 and 8)
-//                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query / IK-query kernels and the mode's launch table
+//                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query / IK-query / contact-query kernels and the mode's launch table
 //   -DDG_LANES=64            -DDG_PART=2  helper-wave step kernels
 //   -DDG_LANES=-16 -DDG_TAG=g16           the global-workspace mode with 16 envs per wavefront
 //   -DDG_MANIFOLD (with any of the above but the helper-wave part): the same kernels with the hull-hull contact manifold compiled
@@ -14,6 +14,7 @@
 #include "dg_dynq.h"
 #if DG_PART == 1
 #include "dg_ikq.h"
+#include "dg_contactq.h"
 #endif
 
 #define DG_CAT_(a, b) a##b
@@ -97,6 +98,9 @@ static void l_joint_targets(dim3 grid, int lds, hipStream_t st, DevScene sc, Mot
 static void l_joint_reset(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, uint64_t joint_mask, const float* q, const float* qd, const uint8_t* env_mask, float* gws) {
   hipLaunchKernelGGL(joint_reset_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, joint_mask, q, qd, env_mask, gws);
 }
+static void l_contacts(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body_a, int link_a, int body_b, int link_b, int32_t* count, int32_t* ids, float* geom, float* force, float* gws) {
+  hipLaunchKernelGGL(contact_query_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body_a, link_a, body_b, link_b, count, ids, geom, force, gws);
+}
 static hipError_t l_prepare(int lds) {
   if (L == 0) return hipSuccess;
   if (L < 0) {  // only the step kernel uses LDS (the sliced sweeps' accumulated impulses)
@@ -107,6 +111,7 @@ static hipError_t l_prepare(int lds) {
   DG_ATTR(reset_kernel<L>); DG_ATTR(observe_kernel<L>); DG_ATTR(frame_kernel<L>); DG_ATTR(wrench_kernel<L>); DG_ATTR(pose_kernel<L>);
   DG_ATTR(joint_state_kernel<L>); DG_ATTR(joint_torque_kernel<L>); DG_ATTR(jacobian_kernel<L>); DG_ATTR(inverse_dynamics_kernel<L>); DG_ATTR(mass_matrix_kernel<L>);
   DG_ATTR(ik_query_kernel<L>); DG_ATTR(joint_targets_kernel<L>); DG_ATTR(joint_reset_kernel<L>);
+  DG_ATTR(contact_query_kernel<L>);
 #undef DG_ATTR
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
   if (e == hipSuccess) e = l_prepare_par_64(lds);
@@ -123,7 +128,8 @@ extern const LaunchTable DGL(g_launch_table) = {
 #endif
     l_reset, l_observe, l_frame, l_wrench, l_pose,
     l_joint_state, l_joint_torque, l_jacobian, l_inverse_dynamics, l_mass_matrix,
-    l_ik_query, l_joint_targets, l_joint_reset};
+    l_ik_query, l_joint_targets, l_joint_reset,
+    l_contacts};
 #endif
 #endif
 

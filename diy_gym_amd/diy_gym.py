@@ -122,6 +122,9 @@ class DIYGym(Receptor):
         # (likewise a lidar's scan: `own_buffers`)
         self._flat_obs_fast = self._flat_fast and not self.builder.cameras and not any(
             getattr(a, 'own_buffers', False) for r in self.receptors.values() for a in r.addons.values())
+        # terminals of compiled addons that are evaluated by a launch of their own after the step (contact_sensor): folded into the
+        # collapsed flag here, since the step kernel's term_flag cannot know them
+        self._late_terminals = [a for r in self.receptors.values() for a in r.addons.values() if getattr(a, 'late_terminal', False)]
         if self.auto_reset and self._has_hook_terminals:
             raise ValueError('auto_reset needs every terminal addon compiled into the step kernel')
 
@@ -232,7 +235,7 @@ class DIYGym(Receptor):
         return walk_dict(ret, self.collapse_rewards_func) if self.collapse_rewards_func is not None else ret
 
     def is_terminal(self):
-        if self.collapse_terminals_func is not None and not self._has_hook_terminals:
+        if self.collapse_terminals_func is not None and not self._has_hook_terminals and not self._late_terminals:
             return self._out(self.sim.term_flag.view(torch.bool))
         ret = self.walk_addons(lambda addon: addon.is_terminal())
         if self._timer_op is not None:
@@ -280,7 +283,7 @@ class DIYGym(Receptor):
         # reward / terminal of the finished step first (they are views of buffers the reset does not write), then the
         # masked reset, which rewrites the observation rows of the envs it restarted
         rew, term = self.reward(), self.is_terminal()
-        self.sim.reset(self.sim.term_flag)
+        self.sim.reset(torch.as_tensor(term, device=self.device).reshape(-1) if self._late_terminals else self.sim.term_flag)
         self._tick += 1
         return self.observe(_refresh=False), rew, term, {}
 

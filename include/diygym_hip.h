@@ -231,6 +231,42 @@ int32_t dg_world_set_joint_targets(dg_world* w, float* state, int32_t body, uint
 int32_t dg_world_reset_joint_state(dg_world* w, float* state, int32_t body, uint64_t joint_mask,
     const float* q, const float* qd /* [num_envs][nv]; qd NULL = zero */, const uint8_t* env_mask /* [num_envs] or NULL = all */, void* stream);
 
+/* Replaces p.getContactPoints(bodyA, bodyB, linkIndexA, linkIndexB) (pybullet's contact readout; the reference itself never calls
+ * it -- none of its addons reads contacts -- so there is no call site to name: this is the query a pybullet user expects, and what
+ * the `contact_sensor` addon is built on).  Every env at once, one launch on `stream`, nothing allocated, freed or synchronised;
+ * the state is not written.  The kernel runs the step's own narrow phase on `state` and reports its contact list, in the order
+ * of the candidate pairs, at most C = the world's max_contacts (DG_H_MAX_CONTACTS of the scene blob) per env -- the step never
+ * has more, so the query never truncates beyond what the solver itself saw.  A world built with hull_manifold_points > 1 reports
+ * the up-to-N points per hull pair that its step sees.
+ *   count [num_envs]          contacts that passed the filter
+ *   ids   [num_envs][C][2]    side A, side B: uid + ((link + 1) << 24) exactly as dg_world_render's seg and dg_world_raycast's id
+ *   geom  [num_envs][C][10]   position on A (3), position on B (3), unit normal on B pointing towards A (3), signed distance
+ *                             (negative: penetration) -- pybullet's positionOnA, positionOnB, contactNormalOnB, contactDistance
+ *   force [num_envs][C]       normal force in newtons (pybullet's normalForce)
+ * ids, geom and force may each be NULL.  EVERY slot of the given arrays is written: behind an env's count the ids are -1 and the
+ * rest 0, so a reused buffer needs no memset and a sum over the C slots is right without a mask.
+ * Filters: body_* is a body index (a Model's uid), link_* a pybullet link index (-1: the base), DG_CONTACT_ANY: no filter; they are
+ * compared with the uid part (id & 0xFFFFFF) and the link part ((id >> 24) - 1) of the ids.  With only body_a given, a contact
+ * that has that body on its B side is reported with the sides swapped and the normal negated: the caller always sees its body as
+ * A and the normal pointing towards it.  With both given either orientation matches and is reported as (a, b).
+ * STALENESS, the rule in full: the geometry is recomputed from the state handed in; the force is the normal impulse the solver
+ * applied IN THE LAST SUBSTEP to the contact with the same key (DG_CONTACT_KEY(pair, feature), the contact impulse cache
+ * DG_WS_*), divided by the substep length.  (pybullet is stale the other way round: its points are those of the last
+ * stepSimulation whatever has been reset since.)  A contact that is new since that substep reports 0 N, and so does one whose
+ * feature changed (a hull resting on a box whose deepest corner is now another one).  After dg_world_reset_joint_state every
+ * force of the env is 0 until the next step; after dg_world_reset the cache is that of the hot-start steps.  Lateral friction is
+ * not reported.
+ * DG_ERR_ARG (nothing launched, outputs untouched): NULL world, state or count; a body out of range; a link the body does not
+ * have (one that neither a shape of the body carries in its id -- the shapes of a rigidly merged child model carry the CHILD's own
+ * link index -- nor is one of the body's frames); a link filter without its body filter.  DG_ERR_UNSUPPORTED: force given in a world without the impulse cache
+ * (DG_H_WARM_OFF < 0: warmstart and warmstart_friction both 0, or no candidate pairs).  A world without candidate pairs answers
+ * DG_OK with every count 0 when force is NULL. */
+#define DG_CONTACT_ANY (-2)
+int32_t dg_world_contacts(dg_world* w, const float* state,
+    int32_t body_a, int32_t link_a, int32_t body_b, int32_t link_b,   /* uid / pybullet link index; DG_CONTACT_ANY (-2) = no filter, link -1 = base */
+    int32_t* count /* [B] */, int32_t* ids /* [B][C][2], may be NULL */, float* geom /* [B][C][10]: posA3 posB3 normal3 dist, may be NULL */,
+    float* force /* [B][C], may be NULL */, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
