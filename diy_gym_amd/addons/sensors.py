@@ -352,3 +352,71 @@ class ContactSensor(Addon):
             return None
         self._evaluate()
         return self.env._out((self._touching & (self._force >= self.force_threshold))[:, 0])
+
+
+class ProximitySensor(Addon):
+    """Clearance of a model from the bodies around it by the batched closest-points query (``env.sim.closest_points`` --
+    pybullet's ``p.getClosestPoints``; the reference ships no such addon).  Goes on a model.  Config keys: ``target`` (the name of
+    another model of the scene; default: any other body), ``frame`` (a joint of the parent: only that link's shapes; default: every
+    link of the parent), ``range`` 0.5 m, ``terminal`` False, ``threshold`` 0.0 m (used with ``terminal``).
+
+    * ``distance`` ``[1]``: the smallest distance between a shape of the parent and a shape of the target, negative when they
+      overlap; ``range`` when nothing is nearer than that.
+    * ``direction`` ``[3]``: the unit vector from the parent towards the nearest body (minus the query's normal); 0 when nothing
+      is within ``range``.
+    * ``is_terminal()`` with ``terminal``: ``distance < threshold``.
+
+    Evaluated by its own two launches (``dg_world_closest`` with ``max_points=0``: the nearest pair alone), lazily, the first time
+    ``observe()`` or ``is_terminal()`` is called after a step."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        from ..model import Model
+        if not isinstance(parent, Model):
+            raise ValueError('proximity_sensor goes on a model, not on the environment')
+        self.uid = parent.uid
+        self.target_name = config.get('target') if 'target' in config else None
+        self.frame_id = None
+        if 'frame' in config:
+            self.frame_id = parent.get_frame_id(config.get('frame'))
+            if self.frame_id < 0:
+                raise ValueError('proximity_sensor: model %r has no joint %r' % (parent.name, config.get('frame')))
+        self.range = float(config.get('range', 0.5))
+        if not (np.isfinite(self.range) and self.range >= 0.0):
+            raise ValueError('proximity_sensor: range must be finite and >= 0, got %r' % (self.range, ))
+        self.terminal = bool(config.get('terminal', False))
+        self.threshold = float(config.get('threshold', 0.0))
+        self.observation_space = spaces.Dict(OrderedDict(distance=spaces.Box(-np.inf, self.range, shape=(1, ), dtype='float32'),
+                                                         direction=spaces.Box(-1., 1., shape=(3, ), dtype='float32')))
+        self.own_buffers = True   # like a lidar's scan, not part of the kernel's observation rows
+        self.late_terminal = self.terminal   # evaluated after the step kernel: the env folds it into the collapsed flag
+        self.target_uid = None
+        self._tick = None
+
+    def compile(self, builder):
+        # (nothing in the scene blob: the filters are run-time arguments of dg_world_closest; every model exists by now)
+        if self.target_name is not None:
+            models = self.env.models
+            if self.target_name not in models:
+                raise ValueError('proximity_sensor: the scene has no model %r' % (self.target_name, ))
+            self.target_uid = models[self.target_name].uid
+
+    def _evaluate(self):
+        env = self.env
+        if self._tick != env._tick:
+            if not hasattr(env.sim, 'closest_points'):
+                raise NotImplementedError('proximity_sensor needs a backend with the batched closest-points query (closest_points); %s has none'
+                                          % type(env.sim).__name__)
+            cp = env.sim.closest_points(self.uid, self.target_uid, self.range, self.frame_id, None, max_points=0, want=('nearest', ))
+            self._distance = cp.nearest_distance.reshape(-1, 1).clone()   # (the backend reuses its output tensors)
+            self._direction = -cp.nearest_normal
+            self._tick = env._tick
+
+    def observe(self):
+        self._evaluate()
+        return OrderedDict(distance=self.env._out(self._distance), direction=self.env._out(self._direction))
+
+    def is_terminal(self):
+        if not self.terminal:
+            return None
+        self._evaluate()
+        return self.env._out(self._distance[:, 0] < self.threshold)

@@ -51,6 +51,9 @@ SYMBOLS = {
     'dg_world_set_joint_targets': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_uint64, _vp, _vp, _vp]),
     'dg_world_reset_joint_state': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     'dg_world_contacts': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
+    'dg_world_closest': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_set_render_diag': (ctypes.c_int32, [_vp, ctypes.c_int32]),
     'dg_world_set_diag_buffer': (ctypes.c_int32, [_vp, _vp]),
     'dg_world_set_profile_buffer': (ctypes.c_int32, [_vp, _vp]),
@@ -92,6 +95,33 @@ RayHits = collections.namedtuple('RayHits', ['frac', 'id', 'pos', 'normal'])
 # what contact_points returns: device tensors, None for the outputs `want` left out (count is always there)
 ContactPoints = collections.namedtuple('ContactPoints', ['count', 'id_a', 'id_b', 'pos_a', 'pos_b', 'normal', 'distance', 'normal_force'])
 CONTACT_ANY = -2   # DG_CONTACT_ANY
+
+# what closest_points returns: device tensors, None for the outputs `want` left out (count is always there)
+ClosestPoints = collections.namedtuple('ClosestPoints', ['count', 'id_a', 'id_b', 'pos_a', 'pos_b', 'normal', 'distance', 'nearest_id_a', 'nearest_id_b',
+                                                         'nearest_pos_a', 'nearest_pos_b', 'nearest_normal', 'nearest_distance'])
+CLOSEST_MAX_POINTS = 64   # the cap of closest_points' default K
+
+
+def closest_candidate_pairs(layout, body_a, link_a, body_b, link_b):
+    """The shape pairs ``dg_world_closest`` tests for a filter, in its row order, from the scene blob alone: side A every shape of
+    ``(body_a, link_a)`` in ascending shape index, side B under it every shape of ``(body_b, link_b)`` -- with ``CONTACT_ANY`` of
+    any other body.  Never a pair: two shapes of one body, visual-only shapes, two shapes neither of which can move, box against
+    box.  Arguments as the C entry takes them (body indices, pybullet link indices, ``CONTACT_ANY``)."""
+    K = _scene_constants()
+    I = layout.I
+    n = int(I[K.H_N_SHAPES])
+    SI = I[I[K.H_OFF_SHAPE_I]:I[K.H_OFF_SHAPE_I] + n * K.SI_STRIDE].reshape(n, K.SI_STRIDE)
+    BI = I[I[K.H_OFF_BODY_I]:I[K.H_OFF_BODY_I] + layout.n_bodies * K.BI_STRIDE].reshape(layout.n_bodies, K.BI_STRIDE)
+    body, link = SI[:, K.SI_BODY], ((SI[:, K.SI_FLAGS] >> 8) & 0xFFFF) - 1
+    solid = (SI[:, K.SI_FLAGS] & K.SHAPE_NO_COLLIDE) == 0
+    moves = ~(((BI[body, K.BI_FLAGS] & K.BODY_FIXED) != 0) & (BI[body, K.BI_N_LINKS] == 0))
+    box = SI[:, K.SI_TYPE] == 1   # DG_SHAPE_BOX
+
+    def match(b, l):
+        return solid & ((b == CONTACT_ANY) | ((body == b) & ((l == CONTACT_ANY) | (link == l))))
+    ma, mb = match(body_a, link_a), match(body_b, link_b)
+    return [(a, c) for a in np.nonzero(ma)[0] for c in np.nonzero(mb)[0]
+            if body[a] != body[c] and (moves[a] or moves[c]) and not (box[a] and box[c])]
 
 
 def debug_plan(layout, num_envs, cu_count=256):
@@ -157,6 +187,8 @@ class HipBackend:
         self._ray_scratch, self._ray_out = None, {}   # ray_test_batch: the pose scratch and the output buffers per `want`
         self._dyn_out = {}   # the dynamics queries' output buffers per (call kind, body)
         self._contact_out = {}   # contact_points: the output buffers per `want`
+        self._closest_scratch, self._closest_out = None, {}   # closest_points: the scratch and the output buffers per (`want`, K)
+        self._closest_k = {}   # ... and the default K per filter
         self._ik_list_cache = {}   # calculate_inverse_kinematics: the null-space lists on the device, per distinct value
         self._check(self.lib.dg_world_init_state(self.handle, _ptr(self.state), self._stream()))
 
@@ -587,6 +619,79 @@ class HipBackend:
         return ContactPoints(count, None if ids is None else ids[:, :C, 0], None if ids is None else ids[:, :C, 1],
                              geom[:, :C, 0:3] if pos else None, geom[:, :C, 3:6] if pos else None, geom[:, :C, 6:9] if nrm else None,
                              geom[:, :C, 9] if dist else None, None if force is None else force[:, :C])
+
+    # -- batched p.getClosestPoints ---------------------------------------------------------------------------------------
+    def closest_points(self, body_a, body_b=None, distance=0.1, link_a=None, link_b=None, max_points=None,
+                       want=('id', 'pos', 'normal', 'distance', 'nearest')):
+        """``p.getClosestPoints(bodyA, bodyB, distance, linkIndexA, linkIndexB)`` for every env at once: every pair of collision
+        shapes of the two sides that is nearer than ``distance`` (penetrating pairs always), the pairs the step never tests because
+        static pruning removed them included.  Returns ``ClosestPoints(count, id_a, id_b, pos_a, pos_b, normal, distance,
+        nearest_id_a, nearest_id_b, nearest_pos_a, nearest_pos_b, nearest_normal, nearest_distance)``: ``count [B]`` int32 (pairs
+        found, whether or not they fit in K: ``count > K`` means the rows were truncated), ``id_a``, ``id_b`` ``[B, K]`` int32 ids
+        as ``contact_points``, ``pos_a``, ``pos_b``, ``normal`` ``[B, K, 3]`` (the normal on B pointing towards A), ``distance
+        [B, K]``; rows in (shape of A, shape of B) order, ids -1 and zeros behind them.  ``nearest_*`` (``[B]``, ``[B, 3]``) is the
+        pair of smallest distance over ALL pairs found, independent of K; with nothing within ``distance`` its ids are -1, positions
+        and normal 0 and ``nearest_distance == distance``, so it serves as an observation as it is.  The groups ``want`` (any of
+        'id', 'pos', 'normal', 'distance', 'nearest') leaves out are None.
+
+        ``body_a`` (required) and ``body_b`` are Models' ``uid`` (None: any other body), ``link_*`` what ``Model.get_frame_id``
+        returns (-1: the base); the alias uid of a merged child is matched as in ``contact_points``.  ``body_a`` is always side A.
+        ``max_points`` K: None = the number of candidate shape pairs of the filter, at most 64.  Each pair is measured in the step's
+        own model of it (``dg_world_closest``); box against box and two bodies that both cannot move are never pairs.  There is no
+        force.  Argument errors raise ValueError.
+
+        The tensors are views of buffers kept per ``(want, K)`` and REUSED by the next call: clone what must last."""
+        groups = ('id', 'pos', 'normal', 'distance', 'nearest')
+        unknown = set(want) - set(groups)
+        if unknown:
+            raise ValueError("want may name 'id', 'pos', 'normal', 'distance', 'nearest', got %r" % (want, ))
+        if body_a is None:
+            raise ValueError('body_a is required (body_b may be None: any other body)')
+        ba, la = self._contact_filter('a', body_a, link_a)
+        bb, lb = self._contact_filter('b', body_b, link_b)
+        distance = float(distance)
+        if not np.isfinite(distance) or distance < 0.0:
+            raise ValueError('distance must be finite and >= 0, got %r' % (distance, ))
+        if max_points is None:
+            key = (ba, la, bb, lb)
+            if key not in self._closest_k:
+                self._closest_k[key] = min(len(closest_candidate_pairs(self.layout, ba, la, bb, lb)), CLOSEST_MAX_POINTS)
+            K = self._closest_k[key]
+        else:
+            K = int(max_points)
+            if K < 0:
+                raise ValueError('max_points must be >= 0, got %d' % K)
+        B = self.num_envs
+        need_ids = 'id' in want and K > 0
+        need_geom = K > 0 and any(g in want for g in ('pos', 'normal', 'distance'))
+        if K > 0 and not (need_ids or need_geom):
+            raise ValueError("max_points %d with none of 'id', 'pos', 'normal', 'distance' wanted: nowhere to put the rows" % K)
+        near = 'nearest' in want
+        key = (need_ids, need_geom, near, K)
+        if key not in self._closest_out:
+            Ks = max(K, 1)   # (K = 0: the buffers still exist, the views are empty)
+            dev = self.device
+            self._closest_out[key] = (torch.zeros((B, ), dtype=torch.int32, device=dev),
+                                      torch.empty((B, Ks, 2), dtype=torch.int32, device=dev) if need_ids else None,
+                                      torch.empty((B, Ks, 10), dtype=torch.float32, device=dev) if need_geom else None,
+                                      torch.empty((B, 2), dtype=torch.int32, device=dev) if near else None,
+                                      torch.empty((B, 10), dtype=torch.float32, device=dev) if near else None)
+        if self._closest_scratch is None:
+            self._closest_scratch = torch.empty((max(int(self.lib.dg_world_closest_scratch_floats(self.handle)), 1), ), dtype=torch.float32,
+                                                device=self.device)
+        count, ids, geom, nids, ngeom = self._closest_out[key]
+        self._dyn_check(self.lib.dg_world_closest(self.handle, _ptr(self.state), ba, la, bb, lb, distance, K, _ptr(self._closest_scratch), _ptr(count),
+                                                  _ptr(ids), _ptr(geom), _ptr(nids), _ptr(ngeom), self._stream()))
+        pos, nrm, dist = K > 0 and 'pos' in want, K > 0 and 'normal' in want, K > 0 and 'distance' in want
+        empty = lambda *s: torch.empty((B, 0) + s, dtype=torch.float32, device=self.device)
+        return ClosestPoints(
+            count,
+            (ids[:, :K, 0] if K > 0 else torch.empty((B, 0), dtype=torch.int32, device=self.device)) if 'id' in want else None,
+            (ids[:, :K, 1] if K > 0 else torch.empty((B, 0), dtype=torch.int32, device=self.device)) if 'id' in want else None,
+            (geom[:, :K, 0:3] if pos else empty(3)) if 'pos' in want else None, (geom[:, :K, 3:6] if pos else empty(3)) if 'pos' in want else None,
+            (geom[:, :K, 6:9] if nrm else empty(3)) if 'normal' in want else None, (geom[:, :K, 9] if dist else empty()) if 'distance' in want else None,
+            nids[:, 0] if near else None, nids[:, 1] if near else None, ngeom[:, 0:3] if near else None, ngeom[:, 3:6] if near else None,
+            ngeom[:, 6:9] if near else None, ngeom[:, 9] if near else None)
 
     def set_render_diag(self, flags):
         """Diagnostic switches of ``render`` (1: no culling -- the brute-force picture; see dg_world_set_render_diag)."""

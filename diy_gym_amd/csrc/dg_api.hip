@@ -81,6 +81,7 @@ struct dg_world {
   int render_diag = 0;  // the plan's at creation (DG_RENDER_NO_CULL / DG_RENDER_DIAG, diagnostics), dg_world_set_render_diag later
   int render_wpe = 2;   // wavefronts per SIMD of the render kernel's build (DG_RENDER_WPE=3: the spilling build)
   int ray_no_cull = 0;  // dg_debug_raycast_no_cull, for tests: every ray against every shape
+  int closest_no_cull = 0;  // dg_debug_closest_no_cull, for tests: every candidate pair through its primitive
   int ray_lds_words = DG_RAY_LDS_WORDS;  // LDS budget of raycast_kernel's staged rows (dg_debug_raycast_lds_words, for tests)
   int ncam = 0; float* d_render_table = nullptr; cip d_CI = nullptr; cfp d_CF = nullptr, d_PLN = nullptr;
   ~dg_world() {  // also the clean-up of a dg_world_create that failed half way
@@ -91,7 +92,7 @@ struct dg_world {
 
 extern "C" {
 
-int32_t dg_version(void) { return (0 << 16) | 8; }
+int32_t dg_version(void) { return (0 << 16) | 9; }
 const char* dg_last_error(void) { return g_err.c_str(); }
 
 int32_t dg_world_create(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int32_t num_envs, int32_t env_stride,
@@ -591,13 +592,13 @@ int32_t dg_world_reset_joint_state(dg_world* w, float* state, int32_t body, uint
 }
 
 // ------------------------------------------------------------------ contact query (dg_contactq.h)
-// a (body, link) filter of dg_world_contacts: 0 or the error code
-static int contact_filter_check(const dg_world* w, int32_t body, int32_t link, const char* side) {
+// a (body, link) filter of dg_world_contacts / dg_world_closest (`what`): 0 or the error code
+static int contact_filter_check(const dg_world* w, int32_t body, int32_t link, const char* side, const char* what = "dg_world_contacts") {
   if (body == DG_CONTACT_ANY) {
-    if (link != DG_CONTACT_ANY) return fail(DG_ERR_ARG, "dg_world_contacts: link_%s %d given without body_%s", side, link, side);
+    if (link != DG_CONTACT_ANY) return fail(DG_ERR_ARG, "%s: link_%s %d given without body_%s", what, side, link, side);
     return DG_OK;
   }
-  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_contacts: body_%s %d out of range", side, body);
+  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "%s: body_%s %d out of range", what, side, body);
   if (link == DG_CONTACT_ANY || link == -1) return DG_OK;
   // A link the body has: one that a shape of the body carries in its id (the value the filter is compared with -- for the shapes of
   // a rigidly merged child model that is the CHILD's own link index), or one of the body's frames (a link without collision shapes)
@@ -607,7 +608,7 @@ static int contact_filter_check(const dg_world* w, int32_t body, int32_t link, c
       if (SI[s * DG_SI_STRIDE + DG_SI_BODY] == body && ((SI[s * DG_SI_STRIDE + DG_SI_FLAGS] >> 8) & 0xFFFF) - 1 == link) return DG_OK;
     if (global_frame(w, body, link) >= 0) return DG_OK;
   }
-  return fail(DG_ERR_ARG, "dg_world_contacts: body %d has no link %d", body, link);
+  return fail(DG_ERR_ARG, "%s: body %d has no link %d", what, body, link);
 }
 
 int32_t dg_world_contacts(dg_world* w, const float* state, int32_t body_a, int32_t link_a, int32_t body_b, int32_t link_b, int32_t* count, int32_t* ids,
@@ -624,6 +625,44 @@ int32_t dg_world_contacts(dg_world* w, const float* state, int32_t body_a, int32
   launch_table(w->lanes, w->mf).contacts(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body_a, link_a, body_b, link_b,
                                          count, ids, geom, force, w->d_gws);
   HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// ------------------------------------------------------------------ closest-points query (dg_closestq.h)
+// floats of the pose table and of the polytope workspace behind it (one block per wavefront of the query's own grid)
+static size_t closest_table_floats(const dg_world* w) { return (size_t)w->num_envs * (size_t)w->sc.nsh * RS_STRIDE; }
+static size_t closest_hull_ws_floats(const dg_world* w) { return (size_t)((w->num_envs + 63) / 64) * (size_t)HH_WS_SLOTS * 64; }
+
+int64_t dg_world_closest_scratch_floats(const dg_world* w) {
+  if (!w) { (void)fail(DG_ERR_ARG, "null world"); return 0; }
+  return (int64_t)(closest_table_floats(w) + closest_hull_ws_floats(w));
+}
+
+int32_t dg_world_closest(dg_world* w, const float* state, int32_t body_a, int32_t link_a, int32_t body_b, int32_t link_b, float distance, int32_t max_points,
+                         float* scratch, int32_t* count, int32_t* ids, float* geom, int32_t* nearest_ids, float* nearest_geom, void* stream) {
+  if (!w || !state) return fail(DG_ERR_ARG, "dg_world_closest: null argument");
+  if (!count) return fail(DG_ERR_ARG, "dg_world_closest: count is NULL (ids, geom, nearest_ids and nearest_geom may be)");
+  if (!scratch) return fail(DG_ERR_ARG, "dg_world_closest: scratch is NULL (dg_world_closest_scratch_floats floats of device memory)");
+  if (body_a == DG_CONTACT_ANY) return fail(DG_ERR_ARG, "dg_world_closest: body_a is required (body_b, link_a and link_b may be DG_CONTACT_ANY)");
+  if (const int rc = contact_filter_check(w, body_a, link_a, "a", "dg_world_closest")) return rc;
+  if (const int rc = contact_filter_check(w, body_b, link_b, "b", "dg_world_closest")) return rc;
+  if (!std::isfinite(distance) || distance < 0.f) return fail(DG_ERR_ARG, "dg_world_closest: distance must be finite and >= 0, got %g", (double)distance);
+  if (max_points < 0) return fail(DG_ERR_ARG, "dg_world_closest: max_points must be >= 0, got %d", max_points);
+  if (max_points > 0 && !ids && !geom) return fail(DG_ERR_ARG, "dg_world_closest: max_points %d with ids and geom both NULL", max_points);
+  DG_ON_DEVICE(w->device);
+  // the shape poses in the world's own workspace mode, then one wavefront per 64 envs: the grid the polytope workspace is sized for
+  launch_table(w->lanes, w->mf).pose(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), 0, w->d_CI, w->d_CF, scratch, w->d_gws, 0, -1, -1);
+  HIP_TRY(hipGetLastError());
+  l_closest(dim3((unsigned)((w->num_envs + 63) / 64)), (hipStream_t)stream, w->sc, scratch, body_a, link_a, body_b, link_b, distance, max_points, w->closest_no_cull,
+            scratch + closest_table_floats(w), count, ids, geom, nearest_ids, nearest_geom);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// diagnostics: dg_world_closest without its culls (what the culled call must equal bit for bit); not part of the public header
+int32_t dg_debug_closest_no_cull(dg_world* w, int32_t on) {
+  if (!w) return fail(DG_ERR_ARG, "null world");
+  w->closest_no_cull = on != 0;
   return DG_OK;
 }
 

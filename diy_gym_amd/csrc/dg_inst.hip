@@ -1,6 +1,7 @@
 // dg_inst.hip -- instantiates the kernels of one envs-per-wavefront mode.  Compiled several times:
 //   -DDG_LANES={64,32,16,8,4,1,0}  -DDG_PART=0  step kernels (+ stamped build for 64, 16 and 8)
 //                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query / IK-query / contact-query kernels and the mode's launch table
+//                                         (+ the closest-points query kernel for 64, which serves every mode)
 //   -DDG_LANES=64            -DDG_PART=2  helper-wave step kernels
 //   -DDG_LANES=-16 -DDG_TAG=g16           the global-workspace mode with 16 envs per wavefront
 //   -DDG_MANIFOLD (with any of the above but the helper-wave part): the same kernels with the hull-hull contact manifold compiled
@@ -15,6 +16,9 @@
 #if DG_PART == 1
 #include "dg_ikq.h"
 #include "dg_contactq.h"
+#if DG_LANES == 64 && !defined(DG_MANIFOLD)
+#include "dg_closestq.h"
+#endif
 #endif
 
 #define DG_CAT_(a, b) a##b
@@ -101,6 +105,12 @@ static void l_joint_reset(dim3 grid, int lds, hipStream_t st, DevScene sc, Motor
 static void l_contacts(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body_a, int link_a, int body_b, int link_b, int32_t* count, int32_t* ids, float* geom, float* force, float* gws) {
   hipLaunchKernelGGL(contact_query_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body_a, link_a, body_b, link_b, count, ids, geom, force, gws);
 }
+#if DG_LANES == 64 && !defined(DG_MANIFOLD)
+void l_closest(dim3 grid, hipStream_t st, DevScene sc, const float* table, int body_a, int link_a, int body_b, int link_b, float distance, int max_points, int no_cull,
+               float* hull_ws, int32_t* count, int32_t* ids, float* geom, int32_t* nearest_ids, float* nearest_geom) {
+  hipLaunchKernelGGL(closest_query_kernel, grid, dim3(64), 0, st, sc, table, body_a, link_a, body_b, link_b, distance, max_points, no_cull, hull_ws, count, ids, geom, nearest_ids, nearest_geom);
+}
+#endif
 static hipError_t l_prepare(int lds) {
   if (L == 0) return hipSuccess;
   if (L < 0) {  // only the step kernel uses LDS (the sliced sweeps' accumulated impulses)

@@ -30,6 +30,9 @@ struct LaunchTable {
   // contact query (dg_contactq.h)
   void (*contacts)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body_a, int link_a, int body_b, int link_b, int32_t* count, int32_t* ids, float* geom, float* force, float* gws);
 };
+// closest-points query (dg_closestq.h): one kernel for every mode -- it uses no workspace -- defined in the 64-lane query unit
+void l_closest(dim3 grid, hipStream_t st, DevScene sc, const float* table, int body_a, int link_a, int body_b, int link_b, float distance, int max_points, int no_cull,
+               float* hull_ws, int32_t* count, int32_t* ids, float* geom, int32_t* nearest_ids, float* nearest_geom);
 const LaunchTable& launch_table(int lanes);  // lanes in {64, 32, 16, 8, 4, 1, 0, -16}
 
 }  // namespace dg

@@ -267,6 +267,40 @@ int32_t dg_world_contacts(dg_world* w, const float* state,
     int32_t* count /* [B] */, int32_t* ids /* [B][C][2], may be NULL */, float* geom /* [B][C][10]: posA3 posB3 normal3 dist, may be NULL */,
     float* force /* [B][C], may be NULL */, void* stream);
 
+/* Replaces p.getClosestPoints(bodyA, bodyB, distance, linkIndexA, linkIndexB) (the reference itself never calls it -- none of its
+ * addons asks for a clearance -- so there is no call site to name: this is the query a pybullet user expects, and what the
+ * `proximity_sensor` addon is built on).  dg_world_contacts stops at the world's contact margin and knows only the pairs the step
+ * tests; this entry reports every pair of shapes nearer than `distance`, the pairs static pruning removed from the step included.
+ * Every env at once, two launches on `stream` (the shape poses, then the query), nothing allocated, freed or synchronised; the
+ * state is not written.  dg_world_closest_scratch_floats: floats of caller-owned device scratch (the per-env shape pose table and
+ * the polytope workspace of the hull-against-hull routine).
+ * Candidate pairs: side A is every shape of (body_a, link_a) in ascending shape index, side B every shape of (body_b, link_b) --
+ * with DG_CONTACT_ANY every shape of ANOTHER body -- in ascending index under each A shape.  Never a pair: two shapes of one body
+ * (a rigidly merged child is its parent's body), visual-only shapes, two shapes neither of which can move, BOX AGAINST BOX (the
+ * step has no routine for it either).  Each pair is measured in the step's own model of it (a hull against a round shape through
+ * the hull's fitted capsule, a hull against a box through the hull's points, two hulls as polytopes in a hull_contacts world with
+ * the hull margin subtracted -- overlapping hulls report the polytope depth), so the distance meets dg_world_contacts' as the
+ * pair closes.
+ *   count        [num_envs]        pairs with distance < `distance` (penetrating pairs always), whether or not they fit in K
+ *   ids          [num_envs][K][2]  side A, side B: uid + ((link + 1) << 24) as dg_world_contacts
+ *   geom         [num_envs][K][10] position on A (3), position on B (3), unit normal on B pointing towards A (3), signed distance
+ *   nearest_ids  [num_envs][2]     the pair of smallest distance over ALL pairs found, independent of K (a tie: the first in pair
+ *   nearest_geom [num_envs][10]    order).  Nothing within `distance`: ids -1, positions and normal 0, the distance field =
+ *                                  `distance` -- usable as an observation as it is.
+ * Rows come in (shape a, shape b) order; rows beyond K = max_points are dropped and still counted: count > K means truncated.
+ * EVERY slot of the given arrays is written: behind the rows the ids are -1 and the rest 0.  The body given as A is always side A.
+ * There is no force: pybullet reports 0 there.  Filters, ids and the alias rule of a merged child are those of dg_world_contacts.
+ * DG_ERR_ARG (nothing launched, outputs untouched): NULL world, state, count or scratch; body_a == DG_CONTACT_ANY; a body out of
+ * range; a link its body does not have; a link filter without its body; distance not finite or < 0; max_points < 0; max_points > 0
+ * with ids and geom both NULL. */
+int64_t dg_world_closest_scratch_floats(const dg_world* w);
+int32_t dg_world_closest(dg_world* w, const float* state,
+    int32_t body_a, int32_t link_a, int32_t body_b, int32_t link_b,  /* body_a required; the others may be DG_CONTACT_ANY */
+    float distance, int32_t max_points /* K >= 0 */, float* scratch,
+    int32_t* count        /* [B]       pairs within `distance`, whether or not they fit in K */,
+    int32_t* ids          /* [B][K][2] may be NULL */, float* geom /* [B][K][10] posA3 posB3 normal3 dist, may be NULL */,
+    int32_t* nearest_ids  /* [B][2]    may be NULL */, float* nearest_geom /* [B][10] may be NULL */, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
