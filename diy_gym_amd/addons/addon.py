@@ -28,11 +28,11 @@ class AddonFactory:
     class _Registry:
         def __init__(self):
             from .controllers import AdmittanceController, InverseKinematicsController, JointController, ExternalForce
-            from .sensors import Camera, ContactSensor, ForceTorqueSensor, JointStateSensor, Lidar, ObjectStateSensor, ProximitySensor
+            from .sensors import Camera, ContactForceSensor, ContactSensor, ForceTorqueSensor, JointStateSensor, Lidar, ObjectStateSensor, ProximitySensor
             from .rewards import ReachTarget, ElectricityCost, TimePenalty
             from .misc import DynamicsRandomizer, Respawn, SpawnMultiple, VisualRandomizer
             from .unsupported import StuckJointCost, DrawCoords
-            # the 17 keys of reference addon.py:36-54, and `lidar`, `contact_sensor` and `proximity_sensor` (no counterpart there)
+            # the 17 keys of reference addon.py:36-54, and `lidar`, `contact_sensor`, `contact_force_sensor` and `proximity_sensor` (no counterpart there)
             self.addons = {
                 'ik_controller': InverseKinematicsController,
                 'joint_controller': JointController,
@@ -53,6 +53,7 @@ class AddonFactory:
                 'dynamics_randomizer': DynamicsRandomizer,
                 'lidar': Lidar,
                 'contact_sensor': ContactSensor,
+                'contact_force_sensor': ContactForceSensor,
                 'proximity_sensor': ProximitySensor,
             }
 

@@ -354,6 +354,73 @@ class ContactSensor(Addon):
         return self.env._out((self._touching & (self._force >= self.force_threshold))[:, 0])
 
 
+class ContactForceSensor(Addon):
+    """Net contact force (and moment) on links of a model by the batched net contact wrench (``env.sim.net_contact_forces`` --
+    normal AND friction forces, what ``contact_sensor`` leaves out; the reference ships no such addon, its ``force_torque_sensor``
+    reads a joint's wrench, not a surface's).  Goes on a model.  Config keys: ``frames`` (a list of joints of the parent: one row
+    per link; default: one row for the whole body), ``target`` (the name of another model of the scene; default: contacts with
+    any body), ``use_torque`` False (needs ``frames``: a moment needs a link to be taken about).
+
+    * ``force`` ``[3 n]``: per row the sum of the forces its contacts apply to the parent, world axes, newtons -- a foot's ground
+      reaction, a finger's grip and traction.
+    * ``torque`` ``[3 n]`` (with ``use_torque``): the sum of their moments about the origin of the link's inertial frame.
+
+    What the solver applied in the last substep (``dg_world_net_contact_wrench`` has the staleness rule); it needs the scene's
+    contact impulse cache (``warmstart`` > 0).  Evaluated by ONE kernel launch of its own, lazily, the first time ``observe()`` is
+    called after a step."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        from ..model import Model
+        if not isinstance(parent, Model):
+            raise ValueError('contact_force_sensor goes on a model, not on the environment')
+        self.uid = parent.uid
+        self.target_name = config.get('target') if 'target' in config else None
+        self.frame_ids = None
+        if 'frames' in config:
+            names = config.get('frames')
+            names = [names] if isinstance(names, str) else list(names)
+            if not 1 <= len(names) <= 16:
+                raise ValueError('contact_force_sensor: frames takes 1 .. 16 joints, got %d' % len(names))
+            self.frame_ids = [parent.get_frame_id(n) for n in names]
+            for n, f in zip(names, self.frame_ids):
+                if f < 0:
+                    raise ValueError('contact_force_sensor: model %r has no joint %r' % (parent.name, n))
+        self.use_torque = bool(config.get('use_torque', False))
+        if self.use_torque and self.frame_ids is None:
+            raise ValueError('contact_force_sensor: use_torque needs frames (the links the moments are taken about)')
+        n = 1 if self.frame_ids is None else len(self.frame_ids)
+        box = lambda: spaces.Box(-np.inf, np.inf, shape=(3 * n, ), dtype='float32')
+        self.observation_space = spaces.Dict(OrderedDict([('force', box())] + ([('torque', box())] if self.use_torque else [])))
+        self.own_buffers = True   # like contact_sensor's, not part of the kernel's observation rows
+        self.target_uid = None
+        self._tick = None
+
+    def compile(self, builder):
+        # (nothing in the scene blob: body, links and filter are run-time arguments of dg_world_net_contact_wrench)
+        if self.target_name is not None:
+            models = self.env.models
+            if self.target_name not in models:
+                raise ValueError('contact_force_sensor: the scene has no model %r' % (self.target_name, ))
+            self.target_uid = models[self.target_name].uid
+
+    def observe(self):
+        env = self.env
+        if self._tick != env._tick:
+            if not hasattr(env.sim, 'net_contact_forces'):
+                raise NotImplementedError('contact_force_sensor needs a backend with the batched net contact wrench (net_contact_forces); %s has none'
+                                          % type(env.sim).__name__)
+            force, torque, _ = env.sim.net_contact_forces(self.uid, self.frame_ids, self.target_uid, None,
+                                                          want=('force', 'torque') if self.use_torque else ('force', ))
+            B = force.shape[0]
+            self._force = force.reshape(B, -1).clone()   # (the backend reuses its output tensors)
+            self._torque = torque.reshape(B, -1).clone() if self.use_torque else None
+            self._tick = env._tick
+        obs = OrderedDict(force=env._out(self._force))
+        if self.use_torque:
+            obs['torque'] = env._out(self._torque)
+        return obs
+
+
 class ProximitySensor(Addon):
     """Clearance of a model from the bodies around it by the batched closest-points query (``env.sim.closest_points`` --
     pybullet's ``p.getClosestPoints``; the reference ships no such addon).  Goes on a model.  Config keys: ``target`` (the name of

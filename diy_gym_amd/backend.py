@@ -51,6 +51,8 @@ SYMBOLS = {
     'dg_world_set_joint_targets': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_uint64, _vp, _vp, _vp]),
     'dg_world_reset_joint_state': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     'dg_world_contacts': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_contact_forces': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    'dg_world_net_contact_wrench': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
     'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
     'dg_world_closest': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -95,6 +97,11 @@ RayHits = collections.namedtuple('RayHits', ['frac', 'id', 'pos', 'normal'])
 # what contact_points returns: device tensors, None for the outputs `want` left out (count is always there)
 ContactPoints = collections.namedtuple('ContactPoints', ['count', 'id_a', 'id_b', 'pos_a', 'pos_b', 'normal', 'distance', 'normal_force'])
 CONTACT_ANY = -2   # DG_CONTACT_ANY
+
+# what contact_forces returns: device tensors, None for the outputs `want` left out (count is always there)
+ContactForces = collections.namedtuple('ContactForces', ['count', 'id_a', 'id_b', 'normal', 'normal_force', 'lateral_friction1', 'lateral_dir1',
+                                                         'lateral_friction2', 'lateral_dir2', 'force_on_a'])
+CONTACT_MAX_LINKS = 16   # DG_CONTACT_MAX_LINKS: link selectors of one net_contact_forces call
 
 # what closest_points returns: device tensors, None for the outputs `want` left out (count is always there)
 ClosestPoints = collections.namedtuple('ClosestPoints', ['count', 'id_a', 'id_b', 'pos_a', 'pos_b', 'normal', 'distance', 'nearest_id_a', 'nearest_id_b',
@@ -187,6 +194,7 @@ class HipBackend:
         self._ray_scratch, self._ray_out = None, {}   # ray_test_batch: the pose scratch and the output buffers per `want`
         self._dyn_out = {}   # the dynamics queries' output buffers per (call kind, body)
         self._contact_out = {}   # contact_points: the output buffers per `want`
+        self._contact_force_out, self._net_contact_out = {}, {}   # contact_forces / net_contact_forces: the output buffers per `want` (and n)
         self._closest_scratch, self._closest_out = None, {}   # closest_points: the scratch and the output buffers per (`want`, K)
         self._closest_k = {}   # ... and the default K per filter
         self._ik_list_cache = {}   # calculate_inverse_kinematics: the null-space lists on the device, per distinct value
@@ -619,6 +627,103 @@ class HipBackend:
         return ContactPoints(count, None if ids is None else ids[:, :C, 0], None if ids is None else ids[:, :C, 1],
                              geom[:, :C, 0:3] if pos else None, geom[:, :C, 3:6] if pos else None, geom[:, :C, 6:9] if nrm else None,
                              geom[:, :C, 9] if dist else None, None if force is None else force[:, :C])
+
+    # -- contact forces in full: lateral friction, per-link net wrench -------------------------------------------------------
+    def contact_forces(self, body_a=None, body_b=None, link_a=None, link_b=None, want=('id', 'force')):
+        """The contact forces ``contact_points`` leaves out, for every env at once.  Returns ``ContactForces(count, id_a, id_b, normal,
+        normal_force, lateral_friction1, lateral_dir1, lateral_friction2, lateral_dir2, force_on_a)``: rows, ``count``, ids, filters
+        and side swapping are exactly ``contact_points``' (same state, same filters: the same rows in the same order);
+        ``normal [B, C, 3]`` and ``normal_force [B, C]`` are its bits; ``lateral_friction1/2 [B, C]`` are the signed friction forces
+        in newtons along the unit tangents ``lateral_dir1/2 [B, C, 3]`` (pybullet's lateralFriction1/2, lateralFrictionDir1/2: the
+        basis the solver's friction rows were built with), and ``force_on_a [B, C, 3]`` is the total force the contact applies to
+        side A in world axes (side B receives its negative)::
+
+            force_on_a = normal_force * normal + lateral_friction1 * lateral_dir1 + lateral_friction2 * lateral_dir2
+
+        Where the filter swaps the sides the normal and both tangents are negated and the scalars kept, so ``(X, Y)`` and ``(Y, X)``
+        report exactly opposite forces.  ``want`` names the groups 'id' and 'force' (everything but the ids); what it leaves out is
+        None.  Behind an env's ``count`` the ids are -1 and everything else 0.
+
+        Staleness as ``contact_points``: geometry and tangents are those of the CURRENT state, the three impulses those of the LAST
+        substep for the contact with the same key, 0 for a new one (``dg_world_contact_forces`` has the rule in full).  A world
+        created with ``warmstart`` and ``warmstart_friction`` both 0 keeps no impulses: RuntimeError.
+
+        The tensors are views of buffers kept per ``want`` and REUSED by the next call: clone what must last."""
+        unknown = set(want) - {'id', 'force'}
+        if unknown:
+            raise ValueError("want may name 'id', 'force', got %r" % (want, ))
+        ba, la = self._contact_filter('a', body_a, link_a)
+        bb, lb = self._contact_filter('b', body_b, link_b)
+        B, C = self.num_envs, int(self.layout.max_contacts)
+        Cs = max(C, 1)
+        key = ('id' in want, 'force' in want)
+        if key not in self._contact_force_out:
+            self._contact_force_out[key] = (torch.zeros((B, ), dtype=torch.int32, device=self.device),
+                                            torch.empty((B, Cs, 2), dtype=torch.int32, device=self.device) if key[0] else None,
+                                            torch.empty((B, Cs, 15), dtype=torch.float32, device=self.device) if key[1] else None)
+        count, ids, f = self._contact_force_out[key]
+        self._dyn_check(self.lib.dg_world_contact_forces(self.handle, _ptr(self.state), ba, la, bb, lb, _ptr(count), _ptr(ids), _ptr(f), self._stream()))
+        if f is None:
+            return ContactForces(count, ids[:, :C, 0] if key[0] else None, ids[:, :C, 1] if key[0] else None, None, None, None, None, None, None, None)
+        return ContactForces(count, None if ids is None else ids[:, :C, 0], None if ids is None else ids[:, :C, 1], f[:, :C, 0:3], f[:, :C, 3],
+                             f[:, :C, 4], f[:, :C, 5:8], f[:, :C, 8], f[:, :C, 9:12], f[:, :C, 12:15])
+
+    def _body_n_frames(self, body):
+        """Frames of a body (the merged children's included), from the scene blob's frame table."""
+        K = _scene_constants()
+        I = self.layout.I
+        n, off = int(I[K.H_N_FRAMES]), int(I[K.H_OFF_FRAME_I])
+        return int((I[off:off + n * K.FI_STRIDE].reshape(n, K.FI_STRIDE)[:, K.FI_BODY] == body).sum())
+
+    def _net_contact_links(self, body, links):
+        """``(body index, [link index or CONTACT_ANY, ...])`` of net_contact_forces' selectors as ``dg_world_net_contact_wrench`` takes
+        them; ValueError for what it would refuse."""
+        body, _ = self._contact_filter('', body, None)
+        if body == CONTACT_ANY:
+            raise ValueError('net_contact_forces needs a body')
+        links = [None] if links is None else list(links)
+        if not 1 <= len(links) <= CONTACT_MAX_LINKS:
+            raise ValueError('net_contact_forces takes 1 .. %d links, got %d' % (CONTACT_MAX_LINKS, len(links)))
+        out = []
+        for l in links:
+            if l is None:
+                out.append(CONTACT_ANY)
+                continue
+            l = int(l)
+            if not -1 <= l < self._body_n_frames(body):
+                raise ValueError('link %d is not a frame of body %d (None: the whole body, -1: the base)' % (l, body))
+            out.append(l)
+        return body, out
+
+    def net_contact_forces(self, body, links=None, body_b=None, link_b=None, want=('force', 'torque', 'count')):
+        """The net contact wrench on links of one body, for every env at once, in ONE launch: ``(force [B, n, 3], torque [B, n, 3],
+        count [B, n])``.  ``body`` is a Model's ``uid``; ``links`` a list of up to 16 of what ``Model.get_frame_id`` returns (-1:
+        the base), each selecting the contacts that have THAT link of the body on a side (for the alias uid of a merged child: frame
+        ids of the PARENT's merged body); ``None`` in the list -- or ``links=None``,
+        one row -- selects the whole body.  ``body_b`` / ``link_b`` optionally restrict the other side, as in ``contact_points``.
+
+        ``force`` is the sum of the forces the selected contacts apply to this body (normal and friction), world axes, in newtons;
+        ``torque`` the sum of their moments about the origin of the link's INERTIAL frame -- the point ``frame_state(body, link,
+        com=True)`` reports; the base's for ``None`` -- with the contact's surface point on this body as the arm; ``count`` int32
+        the number of contacts summed.  What ``want`` leaves out is None.  A link selector must be a frame of the body: the shapes of
+        a merged child model carry the child's own link indices and are reached through the whole-body row and through
+        ``contact_forces``.  Staleness and the impulse cache as ``contact_forces``.
+
+        The tensors are views of buffers kept per number of links and REUSED by the next call: clone what must last."""
+        unknown = set(want) - {'force', 'torque', 'count'}
+        if unknown:
+            raise ValueError("want may name 'force', 'torque', 'count', got %r" % (want, ))
+        body, links = self._net_contact_links(body, links)
+        bb, lb = self._contact_filter('b', body_b, link_b)
+        B, n = self.num_envs, len(links)
+        key = (n, 'count' in want)
+        if key not in self._net_contact_out:
+            self._net_contact_out[key] = (torch.empty((B, n, 6), dtype=torch.float32, device=self.device),
+                                          torch.empty((B, n), dtype=torch.int32, device=self.device) if key[1] else None)
+        wrench, cnt = self._net_contact_out[key]
+        arr = (ctypes.c_int32 * n)(*links)
+        self._dyn_check(self.lib.dg_world_net_contact_wrench(self.handle, _ptr(self.state), body, arr, n, bb, lb, _ptr(wrench), _ptr(cnt), self._stream()))
+        return (wrench[:, :, 0:3] if 'force' in want else None, wrench[:, :, 3:6] if 'torque' in want else None, cnt)
 
     # -- batched p.getClosestPoints ---------------------------------------------------------------------------------------
     def closest_points(self, body_a, body_b=None, distance=0.1, link_a=None, link_b=None, max_points=None,

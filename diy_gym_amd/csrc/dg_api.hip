@@ -92,7 +92,7 @@ struct dg_world {
 
 extern "C" {
 
-int32_t dg_version(void) { return (0 << 16) | 9; }
+int32_t dg_version(void) { return (0 << 16) | 10; }
 const char* dg_last_error(void) { return g_err.c_str(); }
 
 int32_t dg_world_create(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int32_t num_envs, int32_t env_stride,
@@ -624,6 +624,48 @@ int32_t dg_world_contacts(dg_world* w, const float* state, int32_t body_a, int32
   // the grid and block of reset_kernel: one wavefront per workgroup, as many workgroups as the step has (dg_contactq.h, Workspace)
   launch_table(w->lanes, w->mf).contacts(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body_a, link_a, body_b, link_b,
                                          count, ids, geom, force, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// ------------------------------------------------------------------ contact forces (dg_contactf.h)
+int32_t dg_world_contact_forces(dg_world* w, const float* state, int32_t body_a, int32_t link_a, int32_t body_b, int32_t link_b, int32_t* count, int32_t* ids,
+                                float* forces, void* stream) {
+  if (!w || !state) return fail(DG_ERR_ARG, "dg_world_contact_forces: null argument");
+  if (!count) return fail(DG_ERR_ARG, "dg_world_contact_forces: count is NULL (ids and forces may be)");
+  if (const int rc = contact_filter_check(w, body_a, link_a, "a", "dg_world_contact_forces")) return rc;
+  if (const int rc = contact_filter_check(w, body_b, link_b, "b", "dg_world_contact_forces")) return rc;
+  if (w->sc.warm_off < 0)
+    return fail(DG_ERR_UNSUPPORTED, "dg_world_contact_forces: the world keeps no contact impulse cache (warmstart and warmstart_friction are 0, or the scene has "
+                                    "no candidate pairs): no forces to report");
+  DG_ON_DEVICE(w->device);
+  // the grid and block of reset_kernel, as dg_world_contacts (dg_contactq.h, Workspace)
+  launch_table(w->lanes, w->mf).contact_forces(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body_a, link_a, body_b, link_b,
+                                               count, ids, forces, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+int32_t dg_world_net_contact_wrench(dg_world* w, const float* state, int32_t body, const int32_t* links, int32_t n, int32_t body_b, int32_t link_b,
+                                    float* wrench, int32_t* ncontacts, void* stream) {
+  if (!w || !state) return fail(DG_ERR_ARG, "dg_world_net_contact_wrench: null argument");
+  if (!links || !wrench) return fail(DG_ERR_ARG, "dg_world_net_contact_wrench: links or wrench is NULL (ncontacts may be)");
+  if (n < 1 || n > DG_CONTACT_MAX_LINKS) return fail(DG_ERR_ARG, "dg_world_net_contact_wrench: n must be 1 .. %d, got %d", (int)DG_CONTACT_MAX_LINKS, n);
+  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_net_contact_wrench: body %d out of range", body);
+  CfSelectors sel; memset(&sel, 0, sizeof sel); sel.n = n;
+  for (int s = 0; s < n; s++) {  // DG_CONTACT_ANY or a frame of the body: the moment needs the link's inertial frame
+    const int link = links[s]; int gf = -1;
+    if (link != DG_CONTACT_ANY && link != -1 && (link < 0 || (gf = global_frame(w, body, link)) < 0))
+      return fail(DG_ERR_ARG, "dg_world_net_contact_wrench: links[%d] = %d is not a frame of body %d (DG_CONTACT_ANY: the whole body)", s, link, body);
+    sel.link[s] = link; sel.frame[s] = gf;
+  }
+  if (const int rc = contact_filter_check(w, body_b, link_b, "b", "dg_world_net_contact_wrench")) return rc;
+  if (w->sc.warm_off < 0)
+    return fail(DG_ERR_UNSUPPORTED, "dg_world_net_contact_wrench: the world keeps no contact impulse cache (warmstart and warmstart_friction are 0, or the scene "
+                                    "has no candidate pairs): no forces to report");
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).net_contact_wrench(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, sel, body_b, link_b,
+                                                   wrench, ncontacts, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }

@@ -254,8 +254,8 @@ int32_t dg_world_reset_joint_state(dg_world* w, float* state, int32_t body, uint
  * DG_WS_*), divided by the substep length.  (pybullet is stale the other way round: its points are those of the last
  * stepSimulation whatever has been reset since.)  A contact that is new since that substep reports 0 N, and so does one whose
  * feature changed (a hull resting on a box whose deepest corner is now another one).  After dg_world_reset_joint_state every
- * force of the env is 0 until the next step; after dg_world_reset the cache is that of the hot-start steps.  Lateral friction is
- * not reported.
+ * force of the env is 0 until the next step; after dg_world_reset the cache is that of the hot-start steps.  Lateral friction:
+ * dg_world_contact_forces.
  * DG_ERR_ARG (nothing launched, outputs untouched): NULL world, state or count; a body out of range; a link the body does not
  * have (one that neither a shape of the body carries in its id -- the shapes of a rigidly merged child model carry the CHILD's own
  * link index -- nor is one of the body's frames); a link filter without its body filter.  DG_ERR_UNSUPPORTED: force given in a world without the impulse cache
@@ -266,6 +266,61 @@ int32_t dg_world_contacts(dg_world* w, const float* state,
     int32_t body_a, int32_t link_a, int32_t body_b, int32_t link_b,   /* uid / pybullet link index; DG_CONTACT_ANY (-2) = no filter, link -1 = base */
     int32_t* count /* [B] */, int32_t* ids /* [B][C][2], may be NULL */, float* geom /* [B][C][10]: posA3 posB3 normal3 dist, may be NULL */,
     float* force /* [B][C], may be NULL */, void* stream);
+
+/* Contact forces in full: what dg_world_contacts leaves out.  pybullet's getContactPoints also reports lateralFriction1,
+ * lateralFrictionDir1, lateralFriction2 and lateralFrictionDir2; dg_world_contact_forces reports them for every env at once, and
+ * dg_world_net_contact_wrench sums the contact forces per link -- the net contact force tensor of a batched simulator.  Each is one
+ * launch on `stream`; nothing is allocated, freed or synchronised; the state is not written.  Both run the step's own narrow phase
+ * on `state` and look every contact up in the contact impulse cache (DG_WS_*: [key, normal, t1, t2] per contact, written at the end
+ * of every substep), so a world without the cache (DG_H_WARM_OFF < 0: warmstart and warmstart_friction both 0, or no candidate
+ * pairs) answers DG_ERR_UNSUPPORTED to both.
+ *
+ * dg_world_contact_forces: rows, count, ids, filters and side swapping are exactly those of dg_world_contacts (same state, same
+ * filters: the same rows in the same order).  forces [num_envs][C][DG_CFO_STRIDE], columns DG_CFO_*:
+ *   DG_CFO_NORMAL (3)        unit normal on B pointing towards A, as dg_world_contacts
+ *   DG_CFO_NORMAL_FORCE      normal force in newtons, the bits dg_world_contacts reports
+ *   DG_CFO_LATERAL1, _2      friction force along the first / second tangent in newtons, signed (pybullet's lateralFriction1, 2)
+ *   DG_CFO_DIR1, _DIR2 (3)   the unit tangents (lateralFrictionDir1, 2): the basis the solver's friction rows were built with
+ *   DG_CFO_FORCE_A (3)       the total force the contact applies to side A, world axes; side B receives its negative:
+ *                           force_on_a = normal_force x normal + lateral1 x dir1 + lateral2 x dir2
+ * ids and forces may be NULL, count is required; EVERY slot of the given arrays is written: -1 ids and zeros behind the count.
+ * When the filter swaps the sides (dg_world_contacts: the body asked for is always side A), the normal and BOTH tangents are
+ * negated and the three scalars kept, so that (X, Y) and (Y, X) report forces that are exact negatives of each other.  (The
+ * tangents are NOT the basis of the negated normal: that would flip the first tangent only.)
+ *
+ * dg_world_net_contact_wrench: one body, n link selectors links[0 .. n-1] (a HOST array, copied into the kernel's arguments; 1 <= n
+ * <= DG_CONTACT_MAX_LINKS).  A selector is DG_CONTACT_ANY -- the whole body -- or a pybullet link index (-1: the base) that is a
+ * FRAME of the body; body_b / link_b optionally restrict the other side as in dg_world_contacts (DG_CONTACT_ANY: no filter).
+ *   wrench    [num_envs][n][6]  per selector the sum, over the contacts whose side on this body matches the selector, in pair
+ *                               order, of the force on this body (3) and of its moment (3) about the origin of that link's INERTIAL
+ *                               frame -- the point dg_world_frame_state reports with com = 1; for DG_CONTACT_ANY and -1 the base's.
+ *                               The moment arm is the surface point on this body's side (position on A of dg_world_contacts).
+ *   ncontacts [num_envs][n]     contacts summed; may be NULL
+ * Every slot is written exactly once.  The shapes of a rigidly merged child model carry the CHILD's own link indices in their ids:
+ * such an index is not a frame of the body and is refused as a selector here (where it coincides with a frame index of the body,
+ * both match, as in dg_world_contacts) -- those shapes stay reachable through DG_CONTACT_ANY and, link by link, through
+ * dg_world_contact_forces.  A contact between two links of the one body that both match a selector counts once, as side A.
+ *
+ * STALENESS, the rule in full (both entries): the geometry -- points, normal, tangents, moment arms and reference points -- is
+ * recomputed from the state handed in.  The three impulses are those the solver ended the LAST SUBSTEP with for the contact with
+ * the same key (DG_CONTACT_KEY(pair, feature)), divided by the substep length, without the warm-start factors; a contact that is
+ * new since that substep, or whose feature changed, reports 0 in all three.  The tangents are those of the CURRENT normal
+ * (a fixed function of it); for a contact that persists with an unchanged normal that is the basis the impulses were solved in,
+ * and when the normal has turned since, the cached scalars are reported along the turned basis.  After dg_world_reset_joint_state
+ * every force of the env is 0 until the next step.
+ * DG_ERR_ARG (nothing launched, outputs untouched): NULL world, state, count (contact_forces), links or wrench (net wrench); the
+ * filter errors of dg_world_contacts; n < 1 or n > DG_CONTACT_MAX_LINKS; a body out of range; a selector that is not a frame of
+ * the body. */
+enum { DG_CFO_NORMAL = 0, DG_CFO_NORMAL_FORCE = 3, DG_CFO_LATERAL1 = 4, DG_CFO_DIR1 = 5, DG_CFO_LATERAL2 = 8, DG_CFO_DIR2 = 9, DG_CFO_FORCE_A = 12,
+       DG_CFO_STRIDE = 15 };
+#define DG_CONTACT_MAX_LINKS 16
+int32_t dg_world_contact_forces(dg_world* w, const float* state,
+    int32_t body_a, int32_t link_a, int32_t body_b, int32_t link_b,   /* as dg_world_contacts */
+    int32_t* count /* [B] */, int32_t* ids /* [B][C][2], may be NULL */, float* forces /* [B][C][DG_CFO_STRIDE], may be NULL */, void* stream);
+int32_t dg_world_net_contact_wrench(dg_world* w, const float* state, int32_t body,
+    const int32_t* links /* host [n]: DG_CONTACT_ANY or a frame of the body */, int32_t n,
+    int32_t body_b, int32_t link_b,   /* the other side; DG_CONTACT_ANY = no filter */
+    float* wrench /* [B][n][6]: force3 moment3 */, int32_t* ncontacts /* [B][n], may be NULL */, void* stream);
 
 /* Replaces p.getClosestPoints(bodyA, bodyB, distance, linkIndexA, linkIndexB) (the reference itself never calls it -- none of its
  * addons asks for a clearance -- so there is no call site to name: this is the query a pybullet user expects, and what the
