@@ -28,11 +28,11 @@ class AddonFactory:
     class _Registry:
         def __init__(self):
             from .controllers import AdmittanceController, InverseKinematicsController, JointController, ExternalForce
-            from .sensors import Camera, ContactForceSensor, ContactSensor, ForceTorqueSensor, JointStateSensor, Lidar, ObjectStateSensor, ProximitySensor
+            from .sensors import Camera, ContactForceSensor, ContactSensor, ForceTorqueSensor, JointStateSensor, Lidar, LinkStateSensor, ObjectStateSensor, ProximitySensor
             from .rewards import ReachTarget, ElectricityCost, TimePenalty
             from .misc import DynamicsRandomizer, Respawn, SpawnMultiple, VisualRandomizer
             from .unsupported import StuckJointCost, DrawCoords
-            # the 17 keys of reference addon.py:36-54, and `lidar`, `contact_sensor`, `contact_force_sensor` and `proximity_sensor` (no counterpart there)
+            # the 17 keys of reference addon.py:36-54, and `lidar`, `contact_sensor`, `contact_force_sensor`, `proximity_sensor` and `link_state_sensor` (no counterpart there)
             self.addons = {
                 'ik_controller': InverseKinematicsController,
                 'joint_controller': JointController,
@@ -55,6 +55,7 @@ class AddonFactory:
                 'contact_sensor': ContactSensor,
                 'contact_force_sensor': ContactForceSensor,
                 'proximity_sensor': ProximitySensor,
+                'link_state_sensor': LinkStateSensor,
             }
 
     @staticmethod

@@ -487,3 +487,60 @@ class ProximitySensor(Addon):
             return None
         self._evaluate()
         return self.env._out(self._distance[:, 0] < self.threshold)
+
+
+class LinkStateSensor(Addon):
+    """Poses -- and on request velocities -- of several links of a model by the batched link-state query (``env.sim.link_states``
+    -- pybullet's ``p.getLinkStates``; the reference ships no such addon, its ``object_state_sensor`` reads one frame).  A keypoint
+    observation in ONE launch per step.  Goes on a model.  Config keys: ``frames`` (a list of joints of the parent, ``base`` for
+    the base link; default: the base alone), ``com`` False (the links' INERTIAL frames instead of their URDF frames),
+    ``use_velocity`` False.
+
+    Observations are in world coordinates, one row per frame in ``frames`` order:
+
+    * ``position`` ``[3 n]``, ``orientation`` ``[4 n]`` (quaternion xyzw);
+    * with ``use_velocity``, ``velocity`` ``[3 n]`` and ``angular_velocity`` ``[3 n]``.
+
+    Evaluated by its own kernel launch (``dg_world_link_states``), lazily, the first time ``observe()`` is called after a step."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        from ..model import Model
+        if not isinstance(parent, Model):
+            raise ValueError('link_state_sensor goes on a model, not on the environment')
+        self.uid = parent.uid
+        names = config.get('frames') if 'frames' in config else ['base']
+        names = [names] if isinstance(names, str) else list(names)
+        if not 1 <= len(names) <= 32:
+            raise ValueError('link_state_sensor: frames takes 1 .. 32 joints, got %d' % len(names))
+        self.frame_ids = [parent.get_frame_id(n) for n in names]   # (-1, the base, for a name that is no joint: only `base` may be)
+        for n, f in zip(names, self.frame_ids):
+            if f < 0 and n != 'base':
+                raise ValueError('link_state_sensor: model %r has no joint %r' % (parent.name, n))
+        self.com = bool(config.get('com', False))
+        self.use_velocity = bool(config.get('use_velocity', False))
+        n = len(names)
+        box = lambda k, hi=np.inf: spaces.Box(-hi, hi, shape=(k * n, ), dtype='float32')
+        sp = OrderedDict(position=box(3), orientation=box(4, 1.))
+        if self.use_velocity:
+            sp['velocity'], sp['angular_velocity'] = box(3), box(3)
+        self.observation_space = spaces.Dict(sp)
+        self.own_buffers = True   # like contact_sensor's, not part of the kernel's observation rows
+        self._tick = None
+
+    def compile(self, builder):
+        pass   # nothing in the scene blob: the selectors are run-time arguments of dg_world_link_states
+
+    def observe(self):
+        env = self.env
+        if self._tick != env._tick:
+            if not hasattr(env.sim, 'link_states'):
+                raise NotImplementedError('link_state_sensor needs a backend with the batched link-state query (link_states); %s has none'
+                                          % type(env.sim).__name__)
+            st = env.sim.link_states(self.uid, self.frame_ids, com=self.com)
+            B = st.shape[0]
+            cols = lambda a, b: st[:, :, a:b].reshape(B, -1).contiguous()   # (a copy, also for n = 1: the backend reuses its output tensor)
+            self._obs = OrderedDict(position=cols(0, 3), orientation=cols(3, 7))
+            if self.use_velocity:
+                self._obs['velocity'], self._obs['angular_velocity'] = cols(7, 10), cols(10, 13)
+            self._tick = env._tick
+        return OrderedDict((k, env._out(v)) for k, v in self._obs.items())

@@ -53,6 +53,8 @@ SYMBOLS = {
     'dg_world_contacts': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_contact_forces': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]),
     'dg_world_net_contact_wrench': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
+    'dg_world_link_states': (ctypes.c_int32, [_vp, _vp, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
+    'dg_world_reset_base_state': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
     'dg_world_closest': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -107,6 +109,7 @@ CONTACT_MAX_LINKS = 16   # DG_CONTACT_MAX_LINKS: link selectors of one net_conta
 ClosestPoints = collections.namedtuple('ClosestPoints', ['count', 'id_a', 'id_b', 'pos_a', 'pos_b', 'normal', 'distance', 'nearest_id_a', 'nearest_id_b',
                                                          'nearest_pos_a', 'nearest_pos_b', 'nearest_normal', 'nearest_distance'])
 CLOSEST_MAX_POINTS = 64   # the cap of closest_points' default K
+LINK_STATES_MAX = 32   # DG_LINK_STATES_MAX: (body, frame) selectors of one link_states call
 
 
 def closest_candidate_pairs(layout, body_a, link_a, body_b, link_b):
@@ -198,6 +201,7 @@ class HipBackend:
         self._closest_scratch, self._closest_out = None, {}   # closest_points: the scratch and the output buffers per (`want`, K)
         self._closest_k = {}   # ... and the default K per filter
         self._ik_list_cache = {}   # calculate_inverse_kinematics: the null-space lists on the device, per distinct value
+        self._link_states_out = {}   # link_states: the selector arrays and the output buffer per (selectors, com)
         self._check(self.lib.dg_world_init_state(self.handle, _ptr(self.state), self._stream()))
 
     def _stream(self):
@@ -279,6 +283,98 @@ class HipBackend:
         self._check(self.lib.dg_world_frame_state(self.handle, _ptr(self.state), int(body), int(frame), int(bool(com)), _ptr(out),
                                                   self._stream()))
         return out
+
+    # -- batched p.getLinkStates / p.resetBasePositionAndOrientation / p.resetBaseVelocity ------------------------------------
+    def link_states(self, body, frames=None, com=False):
+        """``p.getLinkStates(uid, frames, computeLinkVelocity=1)`` -- and ``getBasePositionAndOrientation`` / ``getBaseVelocity``, frame
+        -1 -- for every env at once, in ONE launch: ``[B, n, 13]``, row k the position (3), quaternion xyzw (4), world linear (3) and
+        angular (3) velocity of frame ``frames[k]``; exactly the bits ``frame_state(body, frames[k], com)`` returns.  ``body`` is a
+        Model's ``uid`` (an attached child model's alias uid included), or a list of uids as long as ``frames`` -- the poses of
+        several models in one call; ``frames`` a list of up to 32 of what ``Model.get_frame_id`` returns (-1: the base; default
+        ``[-1]``).  ``com``: the link's INERTIAL frame instead of its URDF frame, as in ``frame_state``.  The state is not written.
+        Argument errors raise ValueError.
+
+        The result is a view of a buffer kept per ``(selectors, com)`` and REUSED by the next call with the same arguments: clone
+        what must last."""
+        frames = [-1] if frames is None else [int(f) for f in frames]
+        bodies = [int(b) for b in body] if isinstance(body, (list, tuple)) else [int(body)] * len(frames)
+        if len(bodies) != len(frames):
+            raise ValueError('link_states: %d bodies for %d frames (one uid, or one per frame)' % (len(bodies), len(frames)))
+        key = (tuple(bodies), tuple(frames), bool(com))
+        if key not in self._link_states_out:
+            n = len(frames)
+            if not 1 <= n <= LINK_STATES_MAX:
+                raise ValueError('link_states takes 1 .. %d frames, got %d' % (LINK_STATES_MAX, n))
+            sel = []
+            for uid, f in zip(bodies, frames):
+                if f < -1:
+                    raise ValueError('link_states: frame must be a frame id (-1: the base), got %d' % f)
+                b, lf = self.layout.resolve_frame(uid, f)   # (the uid of a merged child model is an alias into its parent's body)
+                if not 0 <= b < self.layout.n_bodies:
+                    raise ValueError('link_states: body %d is not a model of this scene' % uid)
+                if lf >= self._body_n_frames(b):
+                    raise ValueError('link_states: body %d has no frame %d' % (uid, f))
+                sel.append((b, lf))
+            self._link_states_out[key] = ((ctypes.c_int32 * n)(*[b for b, _ in sel]), (ctypes.c_int32 * n)(*[f for _, f in sel]),
+                                          torch.empty((self.num_envs, n, 13), dtype=torch.float32, device=self.device))
+        b_arr, f_arr, out = self._link_states_out[key]
+        self._dyn_check(self.lib.dg_world_link_states(self.handle, _ptr(self.state), b_arr, f_arr, len(frames), int(bool(com)), _ptr(out), self._stream()))
+        return out
+
+    def base_is_movable(self, body):
+        """Whether ``reset_base_state`` takes the body (an index, not an alias): a floating base, or a fixed base that carries a
+        ``respawn`` op -- the planner pins every other fixed base to its load pose (static pair pruning, anchored bounding spheres)."""
+        K = _scene_constants()
+        I = self.layout.I
+        if not self.layout.body_fixed[body]:
+            return True
+        if int(I[int(I[K.H_OFF_BODY_I]) + body * K.BI_STRIDE + K.BI_FLAGS]) & K.BODY_FROZEN:
+            return False
+        n, off = int(I[K.H_N_OPS]), int(I[K.H_OFF_OP_I])
+        OI = I[off:off + n * K.OI_STRIDE].reshape(n, K.OI_STRIDE)
+        return bool(((OI[:, K.OI_CODE] == K.OP_RESPAWN) & (OI[:, K.OI_BODY] == body)).any())
+
+    def _rows4(self, name, v):
+        """``v`` as a contiguous float32 ``[num_envs, 4]`` tensor on this device: one quaternion for every env, or one per env."""
+        if v is None:
+            return None
+        t = torch.as_tensor(v, dtype=torch.float32, device=self.device) if not isinstance(v, torch.Tensor) else v.to(device=self.device, dtype=torch.float32)
+        if t.numel() == 4:
+            t = t.reshape(1, 4).expand(self.num_envs, 4)
+        if t.numel() != 4 * self.num_envs:
+            raise ValueError('%s must have 4 or %d x 4 elements, got shape %s' % (name, self.num_envs, tuple(t.shape)))
+        return t.reshape(self.num_envs, 4).contiguous()
+
+    def reset_base_state(self, body, pos=None, orn=None, lin_vel=None, ang_vel=None, mask=None):
+        """``p.resetBasePositionAndOrientation(uid, pos, orn)`` and ``p.resetBaseVelocity(uid, lin_vel, ang_vel)`` for the envs
+        ``mask`` selects (as for ``reset``; default all).  ``pos`` (``[B, 3]`` or one 3-vector) and ``orn`` (``[B, 4]`` or ``[4]``,
+        xyzw; normalised on the device) go together: the pose of the base's INERTIAL frame, what ``frame_state(uid, -1, com=True)``
+        reports and what the ``respawn`` addon sets.  ``lin_vel`` / ``ang_vel`` (``[B, 3]`` or one 3-vector) are the world velocity of
+        that frame's origin and the world angular velocity, columns 7:13 of the same report.  With a pose, a velocity that is not
+        given becomes zero, as in pybullet; without one only the given velocities change.  Joint state, motor targets and pending
+        external forces stay; the reset envs' contact impulse cache is emptied.  Observations are refreshed by the next
+        ``observe()`` or ``step()``.
+
+        The body must be one whose base the scene lets move: a floating base, or a fixed base with a ``respawn`` addon (zero ranges
+        will do); a fixed base takes no velocity.  Argument errors raise ValueError."""
+        if int(body) in self.layout.aliases:
+            raise ValueError('reset_base_state: model %d is attached to its parent and has no base of its own' % int(body))
+        body = int(body)
+        if not 0 <= body < self.layout.n_bodies:
+            raise ValueError('dg_world_reset_base_state: body %d out of range' % body)
+        if (pos is None) != (orn is None):
+            raise ValueError('dg_world_reset_base_state: pos and orn go together (both or neither)')
+        if pos is None and lin_vel is None and ang_vel is None:
+            raise ValueError('dg_world_reset_base_state: nothing to write (pos, orn, lin_vel and ang_vel are all NULL)')
+        if not self.base_is_movable(body):
+            raise ValueError('dg_world_reset_base_state: body %d has a fixed base that the scene pins to its load pose; add a respawn addon to the model '
+                             '(zero ranges will do) to make its base movable' % body)
+        if self.layout.body_fixed[body] and (lin_vel is not None or ang_vel is not None):
+            raise ValueError('dg_world_reset_base_state: body %d has a fixed base: it takes a pose, no velocity' % body)
+        pos, orn = self._rows3('pos', pos), self._rows4('orn', orn)
+        lin_vel, ang_vel = self._rows3('lin_vel', lin_vel), self._rows3('ang_vel', ang_vel)
+        self._dyn_check(self.lib.dg_world_reset_base_state(self.handle, _ptr(self.state), body, _ptr(pos), _ptr(orn), _ptr(lin_vel), _ptr(ang_vel),
+                                                           _ptr(self._env_mask(mask)), self._stream()))
 
     # -- batched p.applyExternalForce / p.applyExternalTorque for addons written in Python ----------------------------
     LINK_FRAME, WORLD_FRAME = 1, 2   # pybullet's flag values

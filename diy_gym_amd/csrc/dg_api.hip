@@ -591,6 +591,48 @@ int32_t dg_world_reset_joint_state(dg_world* w, float* state, int32_t body, uint
   return DG_OK;
 }
 
+// ------------------------------------------------------------------ link states, base reset (dg_stateq.h)
+int32_t dg_world_link_states(dg_world* w, const float* state, const int32_t* bodies, const int32_t* frames, int32_t n, int32_t com, float* out, void* stream) {
+  if (!w || !state) return fail(DG_ERR_ARG, "dg_world_link_states: null argument");
+  if (!bodies || !frames || !out) return fail(DG_ERR_ARG, "dg_world_link_states: bodies, frames or out is NULL");
+  if (n < 1 || n > DG_LINK_STATES_MAX) return fail(DG_ERR_ARG, "dg_world_link_states: n must be 1 .. %d, got %d", (int)DG_LINK_STATES_MAX, n);
+  LsSelectors sel; memset(&sel, 0, sizeof sel); sel.n = n;
+  for (int k = 0; k < n; k++) {  // what dg_world_frame_state takes, selector by selector
+    const int body = bodies[k], frame = frames[k]; int gf = -1;
+    if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_link_states: bodies[%d] = %d out of range", k, body);
+    if (frame >= 0 && (gf = global_frame(w, body, frame)) < 0) return fail(DG_ERR_ARG, "dg_world_link_states: body %d has no frame %d (selector %d)", body, frame, k);
+    sel.body[k] = body; sel.frame[k] = gf;
+  }
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).link_states(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), sel, com, out, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// A base can be moved only where the planner did not assume it stays at its load pose (scene.py: `frozen`, `anchored` -- static
+// pair pruning, anchored bounding spheres): a floating base, or a fixed base that carries a DG_OP_RESPAWN.  Decided here from the
+// tables the world holds; no scene table has a column for it.
+int32_t dg_world_reset_base_state(dg_world* w, float* state, int32_t body, const float* pos, const float* orn, const float* lin_vel, const float* ang_vel,
+                                  const uint8_t* env_mask, void* stream) {
+  if (!w || !state) return fail(DG_ERR_ARG, "dg_world_reset_base_state: null argument");
+  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_reset_base_state: body %d out of range", body);
+  if ((pos == nullptr) != (orn == nullptr)) return fail(DG_ERR_ARG, "dg_world_reset_base_state: pos and orn go together (both or neither)");
+  if (!pos && !lin_vel && !ang_vel) return fail(DG_ERR_ARG, "dg_world_reset_base_state: nothing to write (pos, orn, lin_vel and ang_vel are all NULL)");
+  const int32_t* I = w->I.data(); const int flags = I[I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE + DG_BI_FLAGS];
+  if (flags & DG_BODY_FIXED) {
+    bool respawned = false; const int32_t* OI = I + I[DG_H_OFF_OP_I];
+    for (int op = 0; op < w->sc.nops; op++) respawned = respawned || (OI[op * DG_OI_STRIDE + DG_OI_CODE] == DG_OP_RESPAWN && OI[op * DG_OI_STRIDE + DG_OI_BODY] == body);
+    if ((flags & DG_BODY_FROZEN) || !respawned)
+      return fail(DG_ERR_ARG, "dg_world_reset_base_state: body %d has a fixed base that the scene pins to its load pose; add a respawn addon to the model "
+                              "(zero ranges will do) to make its base movable", body);
+    if (lin_vel || ang_vel) return fail(DG_ERR_ARG, "dg_world_reset_base_state: body %d has a fixed base: it takes a pose, no velocity", body);
+  }
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).reset_base(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, pos, orn, lin_vel, ang_vel, env_mask, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
 // ------------------------------------------------------------------ contact query (dg_contactq.h)
 // a (body, link) filter of dg_world_contacts / dg_world_closest (`what`): 0 or the error code
 static int contact_filter_check(const dg_world* w, int32_t body, int32_t link, const char* side, const char* what = "dg_world_contacts") {

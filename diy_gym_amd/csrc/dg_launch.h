@@ -9,6 +9,9 @@ namespace dg {
 // ids are compared with (DG_CONTACT_ANY: the whole body) and the global frame whose inertial origin the moment is taken about
 // (-1: the base)
 struct CfSelectors { int32_t n; int32_t link[DG_CONTACT_MAX_LINKS]; int32_t frame[DG_CONTACT_MAX_LINKS]; };
+// the (body, frame) selectors of link_states_kernel (dg_stateq.h), by value in the kernel arguments: the body index and the global
+// frame index (-1: the base)
+struct LsSelectors { int32_t n; int32_t body[DG_LINK_STATES_MAX]; int32_t frame[DG_LINK_STATES_MAX]; };
 
 #define DG_STEP_PARAMS DevScene sc, MotorTable mt, float* state, const float* actions, uint64_t mask, float* obs, float* rew, uint8_t* term, \
                        float* rew_sum, uint8_t* term_flag, int32_t* diag, unsigned long long* cycles
@@ -37,6 +40,9 @@ struct LaunchTable {
   // contact forces (dg_contactf.h)
   void (*contact_forces)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body_a, int link_a, int body_b, int link_b, int32_t* count, int32_t* ids, float* out, float* gws);
   void (*net_contact_wrench)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const CfSelectors& sel, int body_b, int link_b, float* wrench, int32_t* ncontacts, float* gws);
+  // link states, base reset (dg_stateq.h)
+  void (*link_states)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, const LsSelectors& sel, int com, float* out, float* gws);
+  void (*reset_base)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* pos, const float* orn, const float* lin_vel, const float* ang_vel, const uint8_t* env_mask, float* gws);
 };
 // closest-points query (dg_closestq.h): one kernel for every mode -- it uses no workspace -- defined in the 64-lane query unit
 void l_closest(dim3 grid, hipStream_t st, DevScene sc, const float* table, int body_a, int link_a, int body_b, int link_b, float distance, int max_points, int no_cull,

@@ -356,6 +356,48 @@ int32_t dg_world_closest(dg_world* w, const float* state,
     int32_t* ids          /* [B][K][2] may be NULL */, float* geom /* [B][K][10] posA3 posB3 normal3 dist, may be NULL */,
     int32_t* nearest_ids  /* [B][2]    may be NULL */, float* nearest_geom /* [B][10] may be NULL */, void* stream);
 
+/* Link states and base reset: the state reads and the state write the reference's addons make through p.getLinkStates /
+ * p.getLinkState(computeLinkVelocity=1) / p.getBasePositionAndOrientation / p.getBaseVelocity (reference
+ * diy_gym/addons/sensors/object_state_sensor.py:35-42, rewards/reach_target.py:22-28, sensors/camera.py:60-63) and
+ * p.resetBasePositionAndOrientation / p.resetBaseVelocity (misc/respawn.py:35, model.py:68-74), every env at once.  The rules of
+ * the query entries above: device float32 arrays, one launch on `stream`, nothing allocated, freed or synchronised; on DG_ERR_ARG
+ * nothing is launched, outputs are untouched and dg_last_error names the entry.
+ *
+ * dg_world_link_states       n (body, frame) selectors, 1 <= n <= DG_LINK_STATES_MAX, as two HOST arrays copied into the kernel's
+ *                            arguments.  out [num_envs][n][13]: row k of an env is exactly what dg_world_frame_state(body =
+ *                            bodies[k], frame = frames[k], com) writes for that env -- position (3), quaternion xyzw (4), world
+ *                            linear (3) and angular (3) velocity, of the URDF link frame or with com = 1 of the link's inertial
+ *                            frame -- bit for bit: the same device function after the same kinematics, which run once per
+ *                            DISTINCT body among the selectors.  Every (body, frame) dg_world_frame_state takes is taken, a frozen
+ *                            body's base included.  The state is not written.  DG_ERR_ARG: NULL world, state, bodies, frames or
+ *                            out; n out of range; a body out of range; a frame its body does not have.
+ * dg_world_reset_base_state  the base of `body` in the envs env_mask selects (NULL: all).  pos / orn (both or neither) are the pose
+ *                            of the base's INERTIAL frame -- what dg_world_frame_state(body, -1, com = 1) reports in columns 0:7
+ *                            and what the compiled DG_OP_RESPAWN hands to the same device function, so an equal pose is stored as
+ *                            the same bits; orn is normalised on the device.  lin_vel / ang_vel are columns 7:13 of the same
+ *                            report: the world velocity of that frame's origin and the world angular velocity.  The state stores
+ *                            the velocity of the base LINK's origin; the entry converts, so dg_world_frame_state returns what was
+ *                            written.  With a pose, a velocity that is NULL is set to zero (as DG_OP_RESPAWN and pybullet do);
+ *                            with pos and orn NULL only the given velocities change, as p.resetBaseVelocity -- the other keeps its
+ *                            REPORTED value; all four NULL is DG_ERR_ARG.  In the selected envs the contact impulse cache
+ *                            (DG_H_WARM_OFF), where the scene has one, is emptied as dg_world_reset_joint_state does.  Joint
+ *                            state, motor targets, external wrenches, addon state and the step and episode counters are not
+ *                            touched; observations are refreshed by the next dg_world_observe or dg_world_step.
+ *                            WHICH BODIES: a base can be moved only if the planner did not assume it stays at its load pose
+ *                            (static pair pruning, anchored bounding spheres): a floating base, or a fixed base that carries a
+ *                            DG_OP_RESPAWN (a `respawn` addon with zero ranges is how a scene declares a bolted-down body
+ *                            movable).  Any other body -- a frozen one included -- is DG_ERR_ARG with a message that says to add
+ *                            a respawn addon; so is a velocity for a fixed base, pos without orn or the reverse, a body out of
+ *                            range, a NULL world or state. */
+#define DG_LINK_STATES_MAX 32
+int32_t dg_world_link_states(dg_world* w, const float* state,
+    const int32_t* bodies /* host [n] */, const int32_t* frames /* host [n]: pybullet joint index, -1 = base */, int32_t n,
+    int32_t com, float* out /* [num_envs][n][13]: pos3 quat4 linvel3 angvel3 */, void* stream);
+int32_t dg_world_reset_base_state(dg_world* w, float* state, int32_t body,
+    const float* pos /* [B][3] */, const float* orn /* [B][4] xyzw */,      /* both or neither */
+    const float* lin_vel, const float* ang_vel /* [B][3] each, may be NULL */,
+    const uint8_t* env_mask /* [B] or NULL = all */, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
