@@ -544,3 +544,64 @@ class LinkStateSensor(Addon):
                 self._obs['velocity'], self._obs['angular_velocity'] = cols(7, 10), cols(10, 13)
             self._tick = env._tick
         return OrderedDict((k, env._out(v)) for k, v in self._obs.items())
+
+
+class JointWrenchSensor(Addon):
+    """Reaction wrenches across several joints of a model -- and on request the motors' applied torques -- by the batched joint
+    reaction query (``env.sim.joint_reaction_forces`` / ``joint_motor_torques``: the second half of pybullet's ``p.getJointStates``;
+    the reference's ``force_torque_sensor`` reads one joint).  A wrist wrench, torque residuals for collision detection or a load
+    penalty over all joints in ONE launch per step.  Goes on a model.  Config keys: ``frames`` (a list of 1 .. 16 joints of the
+    parent, fixed or movable; default: every movable joint), ``use_motor_torque`` False.
+
+    * ``force`` ``[3 n]``, ``torque`` ``[3 n]``: per joint, in ``frames`` order, what the compiled ``force_torque_sensor`` reports --
+      the force and torque the parent side exerts on the child side, in the inertial frame of the joint's child link, torque about
+      its origin (``env.sim.joint_reaction_forces`` has the semantics and the staleness rule in full).
+    * ``motor_torque`` ``[nv]`` (with ``use_motor_torque``): the torque each motor applied in the last solver pass.
+
+    ``compile()`` makes the scene keep the model's velocities at the start of the last substep
+    (``builder.enable_joint_force_torque``).  Evaluated by ONE kernel launch of its own (two with ``use_motor_torque``), lazily, the
+    first time ``observe()`` is called after a step."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        from ..model import Model
+        if not isinstance(parent, Model):
+            raise ValueError('joint_wrench_sensor goes on a model, not on the environment')
+        self.uid = parent.uid
+        robot = parent.robot
+        if 'frames' in config:
+            names = config.get('frames')
+            names = [names] if isinstance(names, str) else list(names)
+            self.frame_ids = [parent.get_frame_id(n) for n in names]
+            for n, f in zip(names, self.frame_ids):
+                if f < 0:
+                    raise ValueError('joint_wrench_sensor: model %r has no joint %r' % (parent.name, n))
+        else:
+            self.frame_ids = [j.index for j in robot.joints if j.q_index > -1]
+        if not 1 <= len(self.frame_ids) <= 16:
+            raise ValueError('joint_wrench_sensor: frames takes 1 .. 16 joints, got %d' % len(self.frame_ids))
+        self.use_motor_torque = bool(config.get('use_motor_torque', False))
+        n = len(self.frame_ids)
+        box = lambda k: spaces.Box(-np.inf, np.inf, shape=(k, ), dtype='float32')
+        sp = OrderedDict(force=box(3 * n), torque=box(3 * n))
+        if self.use_motor_torque:
+            sp['motor_torque'] = box(sum(1 for j in robot.joints if j.q_index > -1))
+        self.observation_space = spaces.Dict(sp)
+        self.own_buffers = True   # like contact_force_sensor's, not part of the kernel's observation rows
+        self._tick = None
+
+    def compile(self, builder):
+        builder.enable_joint_force_torque(self.uid)   # (the selectors are run-time arguments of dg_world_joint_wrench)
+
+    def observe(self):
+        env = self.env
+        if self._tick != env._tick:
+            if not hasattr(env.sim, 'joint_reaction_forces'):
+                raise NotImplementedError('joint_wrench_sensor needs a backend with the batched joint reaction query (joint_reaction_forces); %s has none'
+                                          % type(env.sim).__name__)
+            w = env.sim.joint_reaction_forces(self.uid, self.frame_ids)
+            B = w.shape[0]
+            self._obs = OrderedDict(force=w[:, :, 0:3].reshape(B, -1).contiguous(), torque=w[:, :, 3:6].reshape(B, -1).contiguous())   # (copies: the backend reuses its output tensor)
+            if self.use_motor_torque:
+                self._obs['motor_torque'] = env.sim.joint_motor_torques(self.uid).clone()
+            self._tick = env._tick
+        return OrderedDict((k, env._out(v)) for k, v in self._obs.items())

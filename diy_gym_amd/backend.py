@@ -21,6 +21,13 @@ _c_i32p = ctypes.POINTER(ctypes.c_int32)
 _c_f64p = ctypes.POINTER(ctypes.c_double)
 _vp = ctypes.c_void_p
 
+
+class JointSelector(ctypes.Structure):
+    """``dg_joint_selector`` of include/diygym_hip.h: one joint of ``dg_world_joint_wrench``."""
+    _fields_ = [('frame', ctypes.c_int32), ('flags', ctypes.c_int32), ('link_mask', ctypes.c_uint64), ('frame_mask', ctypes.c_uint64),
+                ('rigid', ctypes.c_float * 10)]
+
+
 # every symbol include/diygym_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     'dg_version': (ctypes.c_int32, []),
@@ -55,6 +62,8 @@ SYMBOLS = {
     'dg_world_net_contact_wrench': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
     'dg_world_link_states': (ctypes.c_int32, [_vp, _vp, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     'dg_world_reset_base_state': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_joint_wrench': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.POINTER(JointSelector), ctypes.c_int32, _vp, _vp]),
+    'dg_world_joint_efforts': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp]),
     'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
     'dg_world_closest': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -110,6 +119,49 @@ ClosestPoints = collections.namedtuple('ClosestPoints', ['count', 'id_a', 'id_b'
                                                          'nearest_pos_a', 'nearest_pos_b', 'nearest_normal', 'nearest_distance'])
 CLOSEST_MAX_POINTS = 64   # the cap of closest_points' default K
 LINK_STATES_MAX = 32   # DG_LINK_STATES_MAX: (body, frame) selectors of one link_states call
+JOINT_WRENCH_MAX = 16   # DG_JOINT_WRENCH_MAX: joint selectors of one joint_reaction_forces call
+
+
+def joint_wrench_selectors(layout, body, joints=None):
+    """The selectors ``dg_world_joint_wrench`` takes for joints ``joints`` of ``body`` (a Model's ``uid``; what
+    ``Model.get_frame_id`` returns, fixed or movable; None: every movable joint), from the scene alone: ``(body index, joints,
+    (JointSelector * n))``.  The child side of each joint is the compiled sensor's (``FlatBody.ft_cluster``): the rigid cluster of
+    URDF links behind the joint -- the whole moving link when the joint is movable -- plus every moving link hanging off it.
+    ValueError for what the entry would refuse."""
+    K = _scene_constants()
+    body = int(body)
+    if body in layout.aliases:
+        raise ValueError('joint_reaction_forces: model %d is attached to its parent; joint force/torque sensing across the joints of an attached child '
+                         'model is not supported' % body)
+    if not 0 <= body < layout.n_bodies:
+        raise ValueError('dg_world_joint_wrench: body %d out of range' % body)
+    I = layout.I
+    bi = I[int(I[K.H_OFF_BODY_I]) + body * K.BI_STRIDE:][:K.BI_STRIDE]
+    if int(bi[K.BI_FLAGS]) & K.BODY_FROZEN:
+        raise ValueError('dg_world_joint_wrench: body %d is part of the frozen static world: it has no joints' % body)
+    if int(bi[K.BI_PREV_OFF]) < 0:
+        raise ValueError('dg_world_joint_wrench: body %d keeps no saved velocities; call builder.enable_joint_force_torque(body) while the scene is '
+                         'built (joint_wrench_sensor does), or put a compiled force_torque_sensor on the body' % body)
+    flat = layout.flats[body]
+    joints = list(flat.dof_to_joint) if joints is None else [int(j) for j in joints]
+    if not 1 <= len(joints) <= JOINT_WRENCH_MAX:
+        raise ValueError('joint_reaction_forces takes 1 .. %d joints, got %d' % (JOINT_WRENCH_MAX, len(joints)))
+    if len(flat.links) > 64 or len(flat.frames) > 64:
+        raise ValueError('dg_world_joint_wrench: body %d has %d links and %d frames; the selectors\' masks cover 64' % (body, len(flat.links), len(flat.frames)))
+    arr = (JointSelector * len(joints))()
+    for k, j in enumerate(joints):
+        if not 0 <= j < len(flat.frames):
+            raise ValueError('dg_world_joint_wrench: body %d has no frame %d' % (body, j))
+        try:
+            cl = flat.ft_cluster(j)
+        except NotImplementedError as e:   # (a body that carries a merged child model)
+            raise ValueError('dg_world_joint_wrench: %s' % (e, ))
+        m, c, Ic = cl['rigid']
+        arr[k].frame, arr[k].flags = j, (K.FT_WHOLE_LINK if flat.robot.joints[j].movable else 0)
+        arr[k].link_mask = sum(1 << d for d in cl['moving'])
+        arr[k].frame_mask = sum(1 << u for u in cl['urdf_links'])
+        arr[k].rigid[:] = [m, c[0], c[1], c[2], Ic[0, 0], Ic[0, 1], Ic[0, 2], Ic[1, 1], Ic[1, 2], Ic[2, 2]]
+    return body, joints, arr
 
 
 def closest_candidate_pairs(layout, body_a, link_a, body_b, link_b):
@@ -202,6 +254,7 @@ class HipBackend:
         self._closest_k = {}   # ... and the default K per filter
         self._ik_list_cache = {}   # calculate_inverse_kinematics: the null-space lists on the device, per distinct value
         self._link_states_out = {}   # link_states: the selector arrays and the output buffer per (selectors, com)
+        self._joint_wrench_out = {}   # joint_reaction_forces: the selectors and the output buffer per (body, joints)
         self._check(self.lib.dg_world_init_state(self.handle, _ptr(self.state), self._stream()))
 
     def _stream(self):
@@ -561,6 +614,58 @@ class HipBackend:
         if torque is None:
             raise ValueError('torque must be a torch.Tensor, got None')
         self._dyn_check(self.lib.dg_world_apply_joint_torque(self.handle, _ptr(self.state), body, _ptr(self._rows_nv('torque', torque, nv)), self._stream()))
+
+    # -- the second half of p.getJointState(s): jointReactionForces, appliedJointMotorTorque ------------------------------------
+    def joint_reaction_forces(self, body, joints=None):
+        """``p.getJointStates(uid, joints)[..][2]`` after ``p.enableJointForceTorqueSensor`` for every env at once, in ONE launch:
+        ``[B, n, 6]``, row k ``[Fx Fy Fz Mx My Mz]`` of joint ``joints[k]`` -- the force and the torque the PARENT side exerts on
+        the CHILD side through the joint, expressed in the inertial frame of the joint's child link, the torque about that frame's
+        origin: exactly what the compiled ``force_torque_sensor`` reports.  ``body`` is a Model's ``uid``; ``joints`` a list of up
+        to 16 of what ``Model.get_frame_id`` returns, fixed or movable (None: every movable joint of the body, if there are at most
+        16).  The scene must keep the body's velocities at the start of the last substep: ``builder.enable_joint_force_torque(uid)``
+        in an addon's ``compile()`` (``joint_wrench_sensor`` does it), or a compiled ``force_torque_sensor`` on the model.
+
+        The child side is the rigid cluster of URDF links behind the joint (the whole moving link when the joint is movable) plus
+        every moving link hanging off it.  The reading is Newton-Euler over it with the accelerations ``(v_now - v_prev) / h`` of
+        the last substep and gravity taken off, minus the contact forces on child-side shapes; a contact counts when exactly one of
+        its two shapes is on the child side, and its arm is the contact POINT -- the midpoint of ``contact_points``' ``pos_a`` and
+        ``pos_b`` -- as in the compiled sensor, NOT the surface point ``net_contact_forces`` uses.  Motors, applied joint torques
+        and external wrenches are no terms of their own: they show through the motion.
+
+        Staleness as ``contact_forces``: the contact geometry is that of the CURRENT state, the impulses those of the LAST substep
+        for the contact with the same key, 0 for a new one; the compiled sensor reads the last substep's own list, so the two
+        agree to rounding where nothing touches and at rest and differ by one substep of motion while contacts move.  Nothing saves
+        velocities on a teleport: after ``reset_joint_state``, ``reset_base_state`` or a ``set_state`` that changes a velocity the
+        next reading carries the jump ``(v_new - v_prev) / h``; the next step clears it.  After ``reset()`` the accelerations are
+        zero and the cache is empty: the plain gravity load.  The state is not written.
+
+        ValueError: a body without saved velocities, a frozen body or an attached child model, a joint the body does not have, not
+        1 .. 16 joints.  RuntimeError: a world with contact pairs that keeps no contact impulse cache (``warmstart`` and
+        ``warmstart_friction`` both 0).
+
+        The result is a buffer kept per ``(body, joints)`` and REUSED by the next call with the same arguments: clone what must last."""
+        key = (int(body), None if joints is None else tuple(int(j) for j in joints))
+        if key not in self._joint_wrench_out:
+            b, js, arr = joint_wrench_selectors(self.layout, body, joints)
+            self._joint_wrench_out[key] = (b, arr, torch.empty((self.num_envs, len(js), 6), dtype=torch.float32, device=self.device))
+        b, arr, out = self._joint_wrench_out[key]
+        self._dyn_check(self.lib.dg_world_joint_wrench(self.handle, _ptr(self.state), b, arr, len(arr), _ptr(out), self._stream()))
+        return out
+
+    def joint_motor_torques(self, body):
+        """``p.getJointStates(uid, joints)[..][3]`` (appliedJointMotorTorque) for every env: ``[B, nv]``, the motor torque applied to
+        each joint during the last solver pass -- the ``effort`` of ``joint_state_sensor``, what ``electricity_cost`` multiplies with
+        the joint rates.  Any body with joints, fixed or floating base; the alias uid of a merged child gives the PARENT's ``nv``,
+        like ``joint_states``.  The result is a buffer kept per body and REUSED by the next call: clone what must last."""
+        body = self.layout.resolve_frame(body, -1)[0]
+        if not 0 <= body < self.layout.n_bodies:
+            raise ValueError('dg_world_joint_efforts: body %d out of range' % body)
+        nv = int(self.layout.body_n_links[body])
+        if nv < 1:
+            raise ValueError('dg_world_joint_efforts: body %d has no joints' % body)
+        out = self._dyn_buf('effort', body, self.num_envs, nv)
+        self._dyn_check(self.lib.dg_world_joint_efforts(self.handle, _ptr(self.state), body, _ptr(out), self._stream()))
+        return out
 
     # -- batched p.calculateInverseKinematics / POSITION_CONTROL, VELOCITY_CONTROL targets / p.resetJointState ----------------
     # The position-level half of the same contract (reference diy_gym/addons/controllers/ik_controller.py:47-80): same bodies,

@@ -19,6 +19,7 @@
 #include "dg_raycast.h"
 #include "dg_dynq.h"
 #include "dg_ikq.h"
+#include "dg_jointq.h"
 
 using namespace dg;
 
@@ -92,7 +93,7 @@ struct dg_world {
 
 extern "C" {
 
-int32_t dg_version(void) { return (0 << 16) | 10; }
+int32_t dg_version(void) { return (0 << 16) | 11; }
 const char* dg_last_error(void) { return g_err.c_str(); }
 
 int32_t dg_world_create(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int32_t num_envs, int32_t env_stride,
@@ -708,6 +709,54 @@ int32_t dg_world_net_contact_wrench(dg_world* w, const float* state, int32_t bod
   DG_ON_DEVICE(w->device);
   launch_table(w->lanes, w->mf).net_contact_wrench(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, sel, body_b, link_b,
                                                    wrench, ncontacts, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// ------------------------------------------------------------------ joint reaction wrenches, applied motor torques (dg_jointq.h)
+int32_t dg_world_joint_wrench(dg_world* w, const float* state, int32_t body, const dg_joint_selector* selectors, int32_t n, float* wrench, void* stream) {
+  if (!w || !state) return fail(DG_ERR_ARG, "dg_world_joint_wrench: null argument");
+  if (!selectors || !wrench) return fail(DG_ERR_ARG, "dg_world_joint_wrench: selectors or wrench is NULL");
+  if (n < 1 || n > DG_JOINT_WRENCH_MAX) return fail(DG_ERR_ARG, "dg_world_joint_wrench: n must be 1 .. %d, got %d", (int)DG_JOINT_WRENCH_MAX, n);
+  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d out of range", body);
+  const int32_t* I = w->I.data(); const int32_t* B = I + I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE;
+  if (B[DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d is part of the frozen static world: it has no joints", body);
+  if (B[DG_BI_PREV_OFF] < 0)
+    return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d keeps no saved velocities; call builder.enable_joint_force_torque(body) while the scene is built "
+                            "(joint_wrench_sensor does), or put a compiled force_torque_sensor on the body", body);
+  const int nl = B[DG_BI_N_LINKS]; int nfr = 0;
+  for (int f = 0; f < w->sc.nfr; f++) nfr += I[I[DG_H_OFF_FRAME_I] + f * DG_FI_STRIDE + DG_FI_BODY] == body;
+  if (nl > 64 || nfr > 64) return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d has %d links and %d frames; the selectors' masks cover 64", body, nl, nfr);
+  if (jointq_slots(nl) > w->sc.tr_slots)
+    return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d needs %d workspace slots, the world's transient region has %d", body, jointq_slots(nl), w->sc.tr_slots);
+  JwSelectors sel; memset(&sel, 0, sizeof sel); sel.n = n;
+  for (int s = 0; s < n; s++) {
+    const dg_joint_selector& js = selectors[s]; int gf = -1;
+    if (js.frame < 0 || (gf = global_frame(w, body, js.frame)) < 0) return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d has no frame %d (selector %d)", body, js.frame, s);
+    if ((nl < 64 && (js.link_mask >> nl)) || (nfr < 64 && (js.frame_mask >> nfr)))
+      return fail(DG_ERR_ARG, "dg_world_joint_wrench: selector %d names a link or frame past the body's %d links and %d frames", s, nl, nfr);
+    if ((js.flags & DG_FT_WHOLE_LINK) && I[I[DG_H_OFF_FRAME_I] + gf * DG_FI_STRIDE + DG_FI_LINK] < 0)
+      return fail(DG_ERR_ARG, "dg_world_joint_wrench: selector %d asks for the whole moving link of frame %d, which sits on the base", s, js.frame);
+    sel.s[s] = js; sel.s[s].frame = gf;
+  }
+  if (w->sc.npairs > 0 && w->sc.warm_off < 0)
+    return fail(DG_ERR_UNSUPPORTED, "dg_world_joint_wrench: the world keeps no contact impulse cache (warmstart and warmstart_friction are 0): no contact forces "
+                                    "to take off the child side");
+  DG_ON_DEVICE(w->device);
+  // the grid and block of reset_kernel, as dg_world_contacts (dg_contactq.h, Workspace)
+  launch_table(w->lanes, w->mf).joint_wrench(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, sel, wrench, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+int32_t dg_world_joint_efforts(dg_world* w, const float* state, int32_t body, float* out, void* stream) {
+  if (!w || !state || !out) return fail(DG_ERR_ARG, "dg_world_joint_efforts: null argument");
+  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_joint_efforts: body %d out of range", body);
+  const int32_t* I = w->I.data(); const int32_t* B = I + I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE;
+  if (B[DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "dg_world_joint_efforts: body %d is part of the frozen static world: it has no joints", body);
+  if (B[DG_BI_N_LINKS] < 1) return fail(DG_ERR_ARG, "dg_world_joint_efforts: body %d has no joints", body);
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).joint_effort(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, out, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }

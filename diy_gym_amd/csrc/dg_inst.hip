@@ -1,6 +1,6 @@
 // dg_inst.hip -- instantiates the kernels of one envs-per-wavefront mode.  Compiled several times:
 //   -DDG_LANES={64,32,16,8,4,1,0}  -DDG_PART=0  step kernels (+ stamped build for 64, 16 and 8)
-//                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query / IK-query / contact-query / contact-force / link-state kernels and the mode's launch table
+//                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query / IK-query / contact-query / contact-force / link-state / joint-wrench kernels and the mode's launch table
 //                                         (+ the closest-points query kernel for 64, which serves every mode)
 //   -DDG_LANES=64            -DDG_PART=2  helper-wave step kernels
 //   -DDG_LANES=-16 -DDG_TAG=g16           the global-workspace mode with 16 envs per wavefront
@@ -18,6 +18,7 @@
 #include "dg_contactq.h"
 #include "dg_contactf.h"
 #include "dg_stateq.h"
+#include "dg_jointq.h"
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
 #include "dg_closestq.h"
 #endif
@@ -119,6 +120,12 @@ static void l_link_states(dim3 grid, int lds, hipStream_t st, DevScene sc, Motor
 static void l_reset_base(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* pos, const float* orn, const float* lin_vel, const float* ang_vel, const uint8_t* env_mask, float* gws) {
   hipLaunchKernelGGL(reset_base_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, pos, orn, lin_vel, ang_vel, env_mask, gws);
 }
+static void l_joint_wrench(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const JwSelectors& sel, float* wrench, float* gws) {
+  hipLaunchKernelGGL(joint_wrench_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, sel, wrench, gws);
+}
+static void l_joint_effort(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, float* out, float* gws) {
+  hipLaunchKernelGGL(joint_effort_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, out, gws);
+}
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
 void l_closest(dim3 grid, hipStream_t st, DevScene sc, const float* table, int body_a, int link_a, int body_b, int link_b, float distance, int max_points, int no_cull,
                float* hull_ws, int32_t* count, int32_t* ids, float* geom, int32_t* nearest_ids, float* nearest_geom) {
@@ -137,6 +144,7 @@ static hipError_t l_prepare(int lds) {
   DG_ATTR(ik_query_kernel<L>); DG_ATTR(joint_targets_kernel<L>); DG_ATTR(joint_reset_kernel<L>);
   DG_ATTR(contact_query_kernel<L>); DG_ATTR(contact_force_kernel<L>); DG_ATTR(net_contact_wrench_kernel<L>);
   DG_ATTR(link_states_kernel<L>); DG_ATTR(reset_base_kernel<L>);
+  DG_ATTR(joint_wrench_kernel<L>); DG_ATTR(joint_effort_kernel<L>);
 #undef DG_ATTR
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
   if (e == hipSuccess) e = l_prepare_par_64(lds);
@@ -156,7 +164,8 @@ extern const LaunchTable DGL(g_launch_table) = {
     l_ik_query, l_joint_targets, l_joint_reset,
     l_contacts,
     l_contact_forces, l_net_contact_wrench,
-    l_link_states, l_reset_base};
+    l_link_states, l_reset_base,
+    l_joint_wrench, l_joint_effort};
 #endif
 #endif
 

@@ -12,6 +12,9 @@ struct CfSelectors { int32_t n; int32_t link[DG_CONTACT_MAX_LINKS]; int32_t fram
 // the (body, frame) selectors of link_states_kernel (dg_stateq.h), by value in the kernel arguments: the body index and the global
 // frame index (-1: the base)
 struct LsSelectors { int32_t n; int32_t body[DG_LINK_STATES_MAX]; int32_t frame[DG_LINK_STATES_MAX]; };
+// the joint selectors of joint_wrench_kernel (dg_jointq.h), by value in the kernel arguments: dg_joint_selector of the public header
+// with `frame` already the GLOBAL frame index
+struct JwSelectors { int32_t n; int32_t pad_; dg_joint_selector s[DG_JOINT_WRENCH_MAX]; };
 
 #define DG_STEP_PARAMS DevScene sc, MotorTable mt, float* state, const float* actions, uint64_t mask, float* obs, float* rew, uint8_t* term, \
                        float* rew_sum, uint8_t* term_flag, int32_t* diag, unsigned long long* cycles
@@ -43,6 +46,9 @@ struct LaunchTable {
   // link states, base reset (dg_stateq.h)
   void (*link_states)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, const LsSelectors& sel, int com, float* out, float* gws);
   void (*reset_base)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* pos, const float* orn, const float* lin_vel, const float* ang_vel, const uint8_t* env_mask, float* gws);
+  // joint reaction wrenches, applied motor torques (dg_jointq.h)
+  void (*joint_wrench)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const JwSelectors& sel, float* wrench, float* gws);
+  void (*joint_effort)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, float* out, float* gws);
 };
 // closest-points query (dg_closestq.h): one kernel for every mode -- it uses no workspace -- defined in the 64-lane query unit
 void l_closest(dim3 grid, hipStream_t st, DevScene sc, const float* table, int body_a, int link_a, int body_b, int link_b, float distance, int max_points, int no_cull,

@@ -269,6 +269,7 @@ class SceneBuilder:
         self.flist = []
         self.dims = {'act': 0, 'obs': 0, 'rew': 0, 'term': 0}
         self.addon_state = 0
+        self.prev_slots = {}  # body -> addon-state offset of its saved velocities, where enable_joint_force_torque reserved them
         self.n_slots = 0
         self.term_groups = []
 
@@ -338,10 +339,24 @@ class SceneBuilder:
         """Addon-state floats a force_torque_sensor on ``body`` needs for the body's velocities at the start of the last
         substep; 0 when an earlier sensor on the same body already owns them."""
         b = self.resolve(body)[0]
-        if any(row[K.OI_CODE] == K.OP_OBS_FT and row[K.OI_BODY] == b for row, _ in self.ops):
+        if b in self.prev_slots or any(row[K.OI_CODE] == K.OP_OBS_FT and row[K.OI_BODY] == b for row, _ in self.ops):
             return 0
         flat = self.bodies[b][0]
         return len(flat.links) + (0 if flat.fixed_base else 6)
+
+    def enable_joint_force_torque(self, body):
+        """The build-time counterpart of ``p.enableJointForceTorqueSensor``: makes the step keep ``body``'s velocities at the start
+        of its last substep (joint rates in link order, then the base's linear and angular velocity when it floats), which
+        ``env.sim.joint_reaction_forces`` needs for its accelerations.  Reserves ``n_links (+ 6)`` addon-state floats unless the
+        body already owns them -- a compiled ``force_torque_sensor`` on the same body shares them, whichever of the two is compiled
+        first.  A scene that never calls this is laid out as before."""
+        if body in self.aliases:
+            raise NotImplementedError('joint force/torque sensing on an attached child model')
+        b = self.resolve(body)[0]
+        n = self.prev_velocity_slots(b)
+        if n > 0:
+            self.prev_slots[b] = self.addon_state
+            self.addon_state += n
 
     def shapes_of(self, body, urdf_links, moving_dofs):
         """Global indices of the shapes of ``body`` that belong to the given pybullet link indices or sit on one of the
@@ -520,6 +535,8 @@ class SceneBuilder:
                     shape_anchor.append((np.asarray(p_link, dtype=np.float64), (link_reach[sh.link] if sh.link >= 0 else 0.0) + ext))
         addon_off = state_off
         state_dim = state_off + self.addon_state
+        for b, off in self.prev_slots.items():  # enable_joint_force_torque: the body's saved velocities
+            body_i[b][K.BI_PREV_OFF] = addon_off + off
         # per-env dynamics parameters (dynamics_randomizer): the links / bodies they belong to point at the addon state
         for row, _ in self.ops:
             if row[K.OI_CODE] == K.OP_RANDOMIZE_DYNAMICS:
@@ -720,6 +737,7 @@ class SceneLayout:
         self.addon_off = addon_off
         self.state_dim = state_dim
         self.max_contacts = max_contacts
+        self.flats = [b[0] for b in builder.bodies]  # the flattened bodies (FlatBody.ft_cluster: the selectors of joint_reaction_forces)
         self.aliases = dict(builder.aliases)  # uid of an attached child model -> (body, link offset, frame offset, frame that stands for its base)
         self.warm_off = int(I[K.H_WARM_OFF])  # state offset of the contact impulse cache (warm starting), -1: none
         self.physical_dim = self.warm_off if self.warm_off >= 0 else state_dim  # state columns before that cache

@@ -398,6 +398,64 @@ int32_t dg_world_reset_base_state(dg_world* w, float* state, int32_t body,
     const float* lin_vel, const float* ang_vel /* [B][3] each, may be NULL */,
     const uint8_t* env_mask /* [B] or NULL = all */, void* stream);
 
+/* Joint reaction wrenches and applied motor torques: the second half of p.getJointState(s) -- jointReactionForces (after
+ * p.enableJointForceTorqueSensor) and appliedJointMotorTorque (reference diy_gym/addons/sensors/force_torque_sensor.py:14-23,
+ * rewards/electricity_cost.py:13-18), every env at once.  The rules of the query entries above: device float32 arrays, one launch
+ * on `stream`, nothing allocated, freed or synchronised, the state is not written; on an error nothing is launched, outputs are
+ * untouched and dg_last_error names the entry.
+ *
+ * dg_world_joint_wrench   n joint selectors of ONE body, 1 <= n <= DG_JOINT_WRENCH_MAX, as a HOST array copied into the kernel's
+ *                         arguments.  wrench [num_envs][n][6] = [Fx Fy Fz Mx My Mz]: the force and the torque the PARENT side
+ *                         exerts on the CHILD side through the joint `frame` (fixed or movable), expressed in the inertial frame
+ *                         of the joint's child link (DG_FF_COM_* of the frame), the torque about that frame's origin -- exactly
+ *                         what the compiled DG_OP_OBS_FT reports.  The child side is the rigid cluster of URDF links behind the
+ *                         joint -- `rigid`: mass, centre (3) and inertia about it (xx xy xz yy yz zz) in the frame of the moving
+ *                         link the cluster is part of; with DG_FT_WHOLE_LINK in `flags` (a movable joint) the whole moving link
+ *                         from the link table instead -- plus the moving links of `link_mask` (bit i: link i of the body).
+ *                         Newton-Euler over these with the accelerations (v_now - v_prev) / h and gravity taken off, v_prev being
+ *                         the body's velocities at the start of the last substep (DG_BI_PREV_OFF), MINUS the contact forces on
+ *                         child-side shapes: a shape of the body is on the child side when its URDF link is in `frame_mask` (bit
+ *                         j: pybullet link j) or its moving link in `link_mask`, and a contact counts when exactly ONE of its two
+ *                         shapes is.  The arm of a contact force is the contact POINT, the midpoint of dg_world_contacts' position
+ *                         on A and position on B, as in the compiled op -- NOT the surface point dg_world_net_contact_wrench uses.
+ *                         Motors, applied joint torques and external wrenches are no terms of their own: they show through the
+ *                         motion.
+ *                         STALENESS follows dg_world_contact_forces: the contact geometry is that of the narrow phase run on the
+ *                         state handed in, the three impulses the cached ones of the contact with the same key over h, 0 for a
+ *                         new contact.  The compiled op reads the last substep's own list: the two agree to rounding where
+ *                         nothing touches and at rest, and differ by one substep of motion while contacts move.
+ *                         Nothing saves velocities on a teleport: after dg_world_reset_joint_state, dg_world_reset_base_state or a
+ *                         state written by the caller that changes a velocity, the reading carries the jump (v_new - v_prev) / h
+ *                         until the next step; the state of the last step handed in unchanged reads as before.  After
+ *                         dg_world_reset the accelerations are zero and the cache is empty: the plain gravity load, the compiled
+ *                         op's plain-observe mode.
+ *                         DG_ERR_ARG: NULL world, state, selectors or wrench; n out of range; a body out of range, frozen, with
+ *                         more than 64 links or frames, or WITHOUT SAVED VELOCITIES (the message names the remedy:
+ *                         builder.enable_joint_force_torque(body) at build time, or a compiled force_torque_sensor on the body);
+ *                         a frame the body does not have; a mask bit past the body's links or frames; a body whose pose and motion
+ *                         block (21 slots for the base and per link) does not fit the world's transient region.  DG_ERR_UNSUPPORTED, as
+ *                         dg_world_contact_forces: a world with candidate pairs that keeps no contact impulse cache.  A world
+ *                         without candidate pairs has no contact term and is taken.
+ *                         NOT CHECKED: a body that carries a rigidly merged child model.  The shapes of the child carry the child's
+ *                         own URDF link indices, which coincide with bits of the parent's in `frame_mask`, and the rigid numbers of a
+ *                         cluster the child hangs on do not include it: HipBackend refuses such a body (FlatBody.ft_cluster), a
+ *                         direct caller must not pass one.
+ * dg_world_joint_efforts  out [num_envs][n_links]: the motor torque applied to each joint of `body` during the last solver pass
+ *                         (DG_LS_APPLIED; what joint_state_sensor's effort columns and DG_OP_REW_ELECTRICITY read), joints in link
+ *                         order.  Any body with joints, fixed or floating base.  DG_ERR_ARG: NULL world, state or out; a body out
+ *                         of range, frozen or without joints. */
+#define DG_JOINT_WRENCH_MAX 16
+typedef struct dg_joint_selector {
+  int32_t frame;        /* pybullet joint index of the body (the kernels see the global frame index) */
+  int32_t flags;        /* DG_FT_WHOLE_LINK: the joint is movable, the rigid part is its whole moving link */
+  uint64_t link_mask;   /* child-side moving links, bit i = link i of the body */
+  uint64_t frame_mask;  /* URDF links of the rigid cluster, bit j = pybullet link j: shape membership */
+  float rigid[10];      /* mass, com3, inertia xx xy xz yy yz zz of the rigid cluster in its moving link's frame */
+} dg_joint_selector;
+int32_t dg_world_joint_wrench(dg_world* w, const float* state, int32_t body,
+    const dg_joint_selector* selectors /* host [n] */, int32_t n, float* wrench /* [num_envs][n][6]: force3 torque3 */, void* stream);
+int32_t dg_world_joint_efforts(dg_world* w, const float* state, int32_t body, float* out /* [num_envs][n_links] */, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
