@@ -605,3 +605,59 @@ class JointWrenchSensor(Addon):
                 self._obs['motor_torque'] = env.sim.joint_motor_torques(self.uid).clone()
             self._tick = env._tick
         return OrderedDict((k, env._out(v)) for k, v in self._obs.items())
+
+
+class ImuSensor(Addon):
+    """An inertial measurement unit on a model: what an accelerometer and a gyro mounted on one of its links read, by the batched
+    link acceleration query (``env.sim.link_accelerations``; neither pybullet nor the reference has a counterpart).  The sensors a
+    real quadrotor or wheeled robot flies and drives on, in place of the ground-truth world pose of ``object_state_sensor``.  Goes
+    on a model.  Config keys: ``frame`` (a joint of the parent; default the base), ``xyz``, ``rpy`` (the mount in the URDF link
+    frame, exactly ``camera``'s and ``lidar``'s keys and conventions), ``use_gravity`` False.
+
+    * ``linear_acceleration`` ``[3]``: the specific force in sensor axes -- the sensor origin's acceleration over the last substep
+      minus gravity; ``(0, 0, +|g|)`` at rest and level, zero in free fall but for the step's linear damping.
+    * ``angular_velocity`` ``[3]``: in sensor axes.
+    * ``gravity`` ``[3]`` (with ``use_gravity``): the unit gravity direction in sensor axes, ``(0, 0, -1)`` when level.
+
+    ``compile()`` makes the scene keep the model's velocities at the start of the last substep
+    (``builder.enable_joint_force_torque``).  Evaluated by ONE kernel launch of its own, lazily, the first time ``observe()`` is
+    called after a step.  The readings are exact: noise and bias are the user's to add to the tensors."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        from ..mathx import quat_from_euler
+        from ..model import Model
+        if not isinstance(parent, Model):
+            raise ValueError('imu_sensor goes on a model, not on the environment')
+        self.uid = parent.uid
+        self.frame_id = parent.get_frame_id(config.get('frame')) if 'frame' in config else -1
+        if self.frame_id < 0 and 'frame' in config and config.get('frame') != 'base':
+            raise ValueError('imu_sensor: model %r has no joint %r' % (parent.name, config.get('frame')))
+        if parent.flat.fixed_base and len(parent.flat.links) == 0:
+            raise ValueError('imu_sensor: model %r has a fixed base and no joints: it never moves and the scene keeps no velocities for it; '
+                             'its reading would be the constant -g' % parent.name)
+        self.local_pos = [float(v) for v in config.get('xyz', [0., 0., 0.])]
+        self.local_orn = [float(v) for v in quat_from_euler(config.get('rpy', [0., 0., 0.]))]
+        self.use_gravity = bool(config.get('use_gravity', False))
+        box = lambda hi=np.inf: spaces.Box(-hi, hi, shape=(3, ), dtype='float32')
+        sp = OrderedDict(linear_acceleration=box(), angular_velocity=box())
+        if self.use_gravity:
+            sp['gravity'] = box(1.)
+        self.observation_space = spaces.Dict(sp)
+        self.own_buffers = True   # like joint_wrench_sensor's, not part of the kernel's observation rows
+        self._tick = None
+
+    def compile(self, builder):
+        builder.enable_joint_force_torque(self.uid)   # (the selector is a run-time argument of dg_world_link_accelerations)
+
+    def observe(self):
+        env = self.env
+        if self._tick != env._tick:
+            if not hasattr(env.sim, 'link_accelerations'):
+                raise NotImplementedError('imu_sensor needs a backend with the batched link acceleration query (link_accelerations); %s has none'
+                                          % type(env.sim).__name__)
+            r = env.sim.link_accelerations(self.uid, [self.frame_id], self.local_pos, self.local_orn, com=False)
+            self._obs = OrderedDict(linear_acceleration=r.specific_force[:, 0].contiguous(), angular_velocity=r.ang_vel[:, 0].contiguous())   # (copies: the backend reuses its output tensor)
+            if self.use_gravity:
+                self._obs['gravity'] = r.gravity[:, 0].contiguous()
+            self._tick = env._tick
+        return OrderedDict((k, env._out(v)) for k, v in self._obs.items())

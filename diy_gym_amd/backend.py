@@ -28,6 +28,11 @@ class JointSelector(ctypes.Structure):
                 ('rigid', ctypes.c_float * 10)]
 
 
+class AccelSelector(ctypes.Structure):
+    """``dg_accel_selector`` of include/diygym_hip.h: one sensor frame of ``dg_world_link_accelerations``."""
+    _fields_ = [('frame', ctypes.c_int32), ('com', ctypes.c_int32), ('pos', ctypes.c_float * 3), ('quat', ctypes.c_float * 4)]
+
+
 # every symbol include/diygym_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     'dg_version': (ctypes.c_int32, []),
@@ -64,6 +69,7 @@ SYMBOLS = {
     'dg_world_reset_base_state': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_joint_wrench': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.POINTER(JointSelector), ctypes.c_int32, _vp, _vp]),
     'dg_world_joint_efforts': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp]),
+    'dg_world_link_accelerations': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.POINTER(AccelSelector), ctypes.c_int32, _vp, _vp]),
     'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
     'dg_world_closest': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -120,6 +126,63 @@ ClosestPoints = collections.namedtuple('ClosestPoints', ['count', 'id_a', 'id_b'
 CLOSEST_MAX_POINTS = 64   # the cap of closest_points' default K
 LINK_STATES_MAX = 32   # DG_LINK_STATES_MAX: (body, frame) selectors of one link_states call
 JOINT_WRENCH_MAX = 16   # DG_JOINT_WRENCH_MAX: joint selectors of one joint_reaction_forces call
+LINK_ACCEL_MAX = 16   # DG_LINK_ACCEL_MAX: sensor-frame selectors of one link_accelerations call
+# what link_accelerations returns: [B, n, 3] views of ONE [B, n, 15] buffer, at the columns DG_LA_* of include/diygym_hip.h
+LinkAccelerations = collections.namedtuple('LinkAccelerations', ['lin_acc', 'ang_acc', 'specific_force', 'ang_vel', 'gravity'])
+LA_LIN_ACC, LA_ANG_ACC, LA_SPECIFIC_FORCE, LA_ANG_VEL, LA_GRAVITY, LA_STRIDE = 0, 3, 6, 9, 12, 15
+
+
+def _mount_key(v):
+    """A hashable stand-in for a mount argument of ``link_accelerations``: None, one vector or n rows; lists, arrays or tensors."""
+    if v is None:
+        return None
+    if isinstance(v, (list, tuple)) and all(isinstance(x, (int, float)) for x in v):
+        return tuple(v)   # (one vector as a plain list: what imu_sensor passes every tick)
+    return tuple(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64).ravel().tolist())
+
+
+def link_accel_selectors(layout, body, frames=None, local_pos=None, local_orn=None, com=False):
+    """The selectors ``dg_world_link_accelerations`` takes for sensor frames of ``body`` (a Model's ``uid``), from the scene alone:
+    ``(body index, (AccelSelector * n))``.  ``frames``: what ``Model.get_frame_id`` returns, -1 the base (None: the base alone);
+    ``local_pos`` ``[n, 3]`` and ``local_orn`` ``[n, 4]`` xyzw the mount in that frame (one vector: every selector; None: identity).
+    ValueError for what the entry would refuse."""
+    K = _scene_constants()
+    body = int(body)
+    if body in layout.aliases:
+        raise ValueError('link_accelerations: model %d is attached to its parent; acceleration sensing on an attached child model is not '
+                         'supported' % body)
+    if not 0 <= body < layout.n_bodies:
+        raise ValueError('dg_world_link_accelerations: body %d out of range' % body)
+    I = layout.I
+    bi = I[int(I[K.H_OFF_BODY_I]) + body * K.BI_STRIDE:][:K.BI_STRIDE]
+    if int(bi[K.BI_FLAGS]) & K.BODY_FROZEN:
+        raise ValueError('dg_world_link_accelerations: body %d is part of the frozen static world: it never moves' % body)
+    if int(bi[K.BI_PREV_OFF]) < 0:
+        raise ValueError('dg_world_link_accelerations: body %d keeps no saved velocities; call builder.enable_joint_force_torque(body) while the scene '
+                         'is built (imu_sensor does), or put a compiled force_torque_sensor on the body; a fixed base without joints keeps none' % body)
+    frames = [-1] if frames is None else [int(f) for f in frames]
+    n = len(frames)
+    if not 1 <= n <= LINK_ACCEL_MAX:
+        raise ValueError('link_accelerations takes 1 .. %d frames, got %d' % (LINK_ACCEL_MAX, n))
+    nfr = len(layout.flats[body].frames)
+    pos = np.zeros((n, 3)) if local_pos is None else np.array(local_pos, dtype=np.float64)
+    orn = np.tile([0.0, 0.0, 0.0, 1.0], (n, 1)) if local_orn is None else np.array(local_orn, dtype=np.float64)
+    if pos.shape not in ((3, ), (n, 3)) or orn.shape not in ((4, ), (n, 4)):
+        raise ValueError('link_accelerations: local_pos must be [3] or [%d, 3] and local_orn [4] or [%d, 4], got %s and %s' % (n, n, pos.shape, orn.shape))
+    pos, orn = np.broadcast_to(pos, (n, 3)), np.broadcast_to(orn, (n, 4))
+    if not (np.isfinite(pos).all() and np.isfinite(orn).all()):
+        raise ValueError('link_accelerations: local_pos and local_orn must be finite')
+    arr = (AccelSelector * n)()
+    for k, f in enumerate(frames):
+        if not -1 <= f < nfr:
+            raise ValueError('dg_world_link_accelerations: body %d has no frame %d' % (body, f))
+        qn = float(np.linalg.norm(orn[k]))
+        if not qn > 0.0:
+            raise ValueError('dg_world_link_accelerations: the mount quaternion of selector %d has zero norm' % k)
+        arr[k].frame, arr[k].com = f, int(bool(com))
+        arr[k].pos[:] = [float(x) for x in pos[k]]
+        arr[k].quat[:] = [float(x) for x in orn[k] / qn]
+    return body, arr
 
 
 def joint_wrench_selectors(layout, body, joints=None):
@@ -255,6 +318,8 @@ class HipBackend:
         self._ik_list_cache = {}   # calculate_inverse_kinematics: the null-space lists on the device, per distinct value
         self._link_states_out = {}   # link_states: the selector arrays and the output buffer per (selectors, com)
         self._joint_wrench_out = {}   # joint_reaction_forces: the selectors and the output buffer per (body, joints)
+        self._link_accel_out = {}   # link_accelerations: the output buffer (its pointer and its five views) per number of selectors
+        self._link_accel_sel = {}   # ... and the selectors per distinct arguments
         self._check(self.lib.dg_world_init_state(self.handle, _ptr(self.state), self._stream()))
 
     def _stream(self):
@@ -666,6 +731,50 @@ class HipBackend:
         out = self._dyn_buf('effort', body, self.num_envs, nv)
         self._dyn_check(self.lib.dg_world_joint_efforts(self.handle, _ptr(self.state), body, _ptr(out), self._stream()))
         return out
+
+    # -- how links accelerate, and what an IMU on one reads (no pybullet counterpart) --------------------------------------------
+    def link_accelerations(self, body, frames=None, local_pos=None, local_orn=None, com=False):
+        """How links of ``body`` ACCELERATE and what an accelerometer and a gyro mounted on them read, for every env at once, in ONE
+        launch.  A named tuple ``(lin_acc, ang_acc, specific_force, ang_vel, gravity)``, each a ``[B, n, 3]`` view of one
+        ``[B, n, 15]`` buffer.  ``body`` is a Model's ``uid``; ``frames`` up to 16 of what ``Model.get_frame_id`` returns, -1 the base
+        (None: the base alone); ``com`` False: the URDF link frame ``camera`` and ``lidar`` mount on, True: the link's inertial frame,
+        as ``link_states``; ``local_pos`` ``[n, 3]`` and ``local_orn`` ``[n, 4]`` xyzw a mount pose in that frame (one vector applies
+        to every selector; default identity).
+
+        With S the sensor frame (world rotation ``R_s``, origin ``p_s``), L the moving link it is rigidly attached to, ``w, alpha,
+        a`` that link's angular velocity and accelerations -- ``(v_now - v_prev) / h`` over the LAST SUBSTEP, as
+        ``joint_reaction_forces`` forms them -- ``r = p_s - p_L`` and ``g`` the scene's gravity:
+
+        * ``lin_acc`` = ``a + alpha x r + w x (w x r)`` and ``ang_acc`` = ``alpha``, world axes;
+        * ``specific_force`` = ``R_s^T (lin_acc - g)``: what an accelerometer reads, ``(0, 0, +|g|)`` at rest and level;
+        * ``ang_vel`` = ``R_s^T w``: what a gyro reads;
+        * ``gravity`` = ``R_s^T g / |g|`` (zeros when ``g = 0``): the projected gravity direction.
+
+        No contact term and no narrow phase: contact, motor and external forces show through the motion.  The scene must keep the
+        body's velocities at the start of the last substep: ``builder.enable_joint_force_torque(uid)`` in an addon's ``compile()``
+        (``imu_sensor`` does it), or a compiled ``force_torque_sensor`` on the model.  Nothing saves velocities on a teleport: after
+        ``reset_joint_state``, ``reset_base_state`` or a ``set_state`` that changes a velocity the next reading carries the jump
+        ``(v_new - v_prev) / h``; the next step clears it.  After ``reset()`` the accelerations are zero and ``specific_force`` is
+        ``-R_s^T g``.  The state is not written.  Sensor noise and bias are the caller's to add to the tensors.
+
+        ValueError, before any launch: a body without saved velocities (a fixed base without joints keeps none: its reading is the
+        constant ``-g``), a frozen body or an attached child model, a frame the body does not have, not 1 .. 16 frames, a mount
+        quaternion of zero norm.
+
+        The buffer is kept per ``n`` and REUSED by the next call with as many frames: clone what must last."""
+        key = (int(body), None if frames is None else tuple(frames), _mount_key(local_pos), _mount_key(local_orn), bool(com))
+        hit = self._link_accel_sel.get(key)
+        if hit is None:
+            b, arr = link_accel_selectors(self.layout, body, frames, local_pos, local_orn, com)
+            n = len(arr)
+            if n not in self._link_accel_out:
+                out = torch.empty((self.num_envs, n, LA_STRIDE), dtype=torch.float32, device=self.device)
+                views = LinkAccelerations(*(out[:, :, k:k + 3] for k in (LA_LIN_ACC, LA_ANG_ACC, LA_SPECIFIC_FORCE, LA_ANG_VEL, LA_GRAVITY)))
+                self._link_accel_out[n] = (_ptr(out), views)
+            hit = self._link_accel_sel[key] = (b, arr, n) + self._link_accel_out[n]
+        b, arr, n, out_ptr, views = hit
+        self._dyn_check(self.lib.dg_world_link_accelerations(self.handle, _ptr(self.state), b, arr, n, out_ptr, self._stream()))
+        return views
 
     # -- batched p.calculateInverseKinematics / POSITION_CONTROL, VELOCITY_CONTROL targets / p.resetJointState ----------------
     # The position-level half of the same contract (reference diy_gym/addons/controllers/ik_controller.py:47-80): same bodies,

@@ -20,6 +20,7 @@
 #include "dg_dynq.h"
 #include "dg_ikq.h"
 #include "dg_jointq.h"
+#include "dg_accelq.h"
 
 using namespace dg;
 
@@ -93,7 +94,7 @@ struct dg_world {
 
 extern "C" {
 
-int32_t dg_version(void) { return (0 << 16) | 11; }
+int32_t dg_version(void) { return (0 << 16) | 12; }
 const char* dg_last_error(void) { return g_err.c_str(); }
 
 int32_t dg_world_create(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int32_t num_envs, int32_t env_stride,
@@ -757,6 +758,39 @@ int32_t dg_world_joint_efforts(dg_world* w, const float* state, int32_t body, fl
   if (B[DG_BI_N_LINKS] < 1) return fail(DG_ERR_ARG, "dg_world_joint_efforts: body %d has no joints", body);
   DG_ON_DEVICE(w->device);
   launch_table(w->lanes, w->mf).joint_effort(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, out, w->d_gws);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+
+// ------------------------------------------------------------------ link accelerations, IMU readings (dg_accelq.h)
+int32_t dg_world_link_accelerations(dg_world* w, const float* state, int32_t body, const dg_accel_selector* selectors, int32_t n, float* out, void* stream) {
+  if (!w || !state) return fail(DG_ERR_ARG, "dg_world_link_accelerations: null argument");
+  if (!selectors || !out) return fail(DG_ERR_ARG, "dg_world_link_accelerations: selectors or out is NULL");
+  if (n < 1 || n > DG_LINK_ACCEL_MAX) return fail(DG_ERR_ARG, "dg_world_link_accelerations: n must be 1 .. %d, got %d", (int)DG_LINK_ACCEL_MAX, n);
+  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d out of range", body);
+  const int32_t* I = w->I.data(); const int32_t* B = I + I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE;
+  if (B[DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d is part of the frozen static world: it never moves", body);
+  if (B[DG_BI_PREV_OFF] < 0)
+    return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d keeps no saved velocities; call builder.enable_joint_force_torque(body) while the scene is built "
+                            "(imu_sensor does), or put a compiled force_torque_sensor on the body; a fixed base without joints keeps none", body);
+  const int nl = B[DG_BI_N_LINKS];
+  if (jointq_slots(nl) > w->sc.tr_slots)
+    return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d needs %d workspace slots, the world's transient region has %d", body, jointq_slots(nl), w->sc.tr_slots);
+  LaSelectors sel; memset(&sel, 0, sizeof sel); sel.n = n;
+  for (int s = 0; s < n; s++) {
+    const dg_accel_selector& as = selectors[s]; int gf = -1;
+    if (as.frame < -1 || (as.frame >= 0 && (gf = global_frame(w, body, as.frame)) < 0))
+      return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d has no frame %d (selector %d)", body, as.frame, s);
+    const double qn = std::sqrt((double)as.quat[0] * as.quat[0] + (double)as.quat[1] * as.quat[1] + (double)as.quat[2] * as.quat[2] + (double)as.quat[3] * as.quat[3]);
+    if (!(qn > 0.0) || !std::isfinite(qn)) return fail(DG_ERR_ARG, "dg_world_link_accelerations: the mount quaternion of selector %d has zero norm", s);
+    sel.s[s] = as; sel.s[s].frame = gf; sel.s[s].com = as.com != 0;
+    for (int k = 0; k < 4; k++) sel.s[s].quat[k] = (float)(as.quat[k] / qn);
+  }
+  const double gn = std::sqrt((double)w->sc.gx * w->sc.gx + (double)w->sc.gy * w->sc.gy + (double)w->sc.gz * w->sc.gz);
+  if (gn > 0.0) { sel.ghat[0] = (float)(w->sc.gx / gn); sel.ghat[1] = (float)(w->sc.gy / gn); sel.ghat[2] = (float)(w->sc.gz / gn); }
+  DG_ON_DEVICE(w->device);
+  // the grid and block of reset_kernel, as dg_world_joint_wrench
+  launch_table(w->lanes, w->mf).link_accel(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, sel, out, w->d_gws);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }

@@ -1,6 +1,6 @@
 // dg_inst.hip -- instantiates the kernels of one envs-per-wavefront mode.  Compiled several times:
 //   -DDG_LANES={64,32,16,8,4,1,0}  -DDG_PART=0  step kernels (+ stamped build for 64, 16 and 8)
-//                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query / IK-query / contact-query / contact-force / link-state / joint-wrench kernels and the mode's launch table
+//                            -DDG_PART=1  reset / observe / frame / pose / dynamics-query / IK-query / contact-query / contact-force / link-state / joint-wrench / link-acceleration kernels and the mode's launch table
 //                                         (+ the closest-points query kernel for 64, which serves every mode)
 //   -DDG_LANES=64            -DDG_PART=2  helper-wave step kernels
 //   -DDG_LANES=-16 -DDG_TAG=g16           the global-workspace mode with 16 envs per wavefront
@@ -19,6 +19,7 @@
 #include "dg_contactf.h"
 #include "dg_stateq.h"
 #include "dg_jointq.h"
+#include "dg_accelq.h"
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
 #include "dg_closestq.h"
 #endif
@@ -126,6 +127,9 @@ static void l_joint_wrench(dim3 grid, int lds, hipStream_t st, DevScene sc, Moto
 static void l_joint_effort(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, float* out, float* gws) {
   hipLaunchKernelGGL(joint_effort_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, out, gws);
 }
+static void l_link_accel(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const LaSelectors& sel, float* out, float* gws) {
+  hipLaunchKernelGGL(link_accel_kernel<L>, grid, dim3(64), lds, st, sc, mt, state, body, sel, out, gws);
+}
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
 void l_closest(dim3 grid, hipStream_t st, DevScene sc, const float* table, int body_a, int link_a, int body_b, int link_b, float distance, int max_points, int no_cull,
                float* hull_ws, int32_t* count, int32_t* ids, float* geom, int32_t* nearest_ids, float* nearest_geom) {
@@ -145,6 +149,7 @@ static hipError_t l_prepare(int lds) {
   DG_ATTR(contact_query_kernel<L>); DG_ATTR(contact_force_kernel<L>); DG_ATTR(net_contact_wrench_kernel<L>);
   DG_ATTR(link_states_kernel<L>); DG_ATTR(reset_base_kernel<L>);
   DG_ATTR(joint_wrench_kernel<L>); DG_ATTR(joint_effort_kernel<L>);
+  DG_ATTR(link_accel_kernel<L>);
 #undef DG_ATTR
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
   if (e == hipSuccess) e = l_prepare_par_64(lds);
@@ -165,7 +170,8 @@ extern const LaunchTable DGL(g_launch_table) = {
     l_contacts,
     l_contact_forces, l_net_contact_wrench,
     l_link_states, l_reset_base,
-    l_joint_wrench, l_joint_effort};
+    l_joint_wrench, l_joint_effort,
+    l_link_accel};
 #endif
 #endif
 

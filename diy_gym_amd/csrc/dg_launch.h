@@ -15,6 +15,10 @@ struct LsSelectors { int32_t n; int32_t body[DG_LINK_STATES_MAX]; int32_t frame[
 // the joint selectors of joint_wrench_kernel (dg_jointq.h), by value in the kernel arguments: dg_joint_selector of the public header
 // with `frame` already the GLOBAL frame index
 struct JwSelectors { int32_t n; int32_t pad_; dg_joint_selector s[DG_JOINT_WRENCH_MAX]; };
+// the sensor-frame selectors of link_accel_kernel (dg_accelq.h), by value in the kernel arguments: dg_accel_selector of the public
+// header with `frame` already the GLOBAL frame index (-1: the base) and `quat` normalised; ghat is the scene's gravity direction
+// g / |g| (zeros when g = 0)
+struct LaSelectors { int32_t n; float ghat[3]; dg_accel_selector s[DG_LINK_ACCEL_MAX]; };
 
 #define DG_STEP_PARAMS DevScene sc, MotorTable mt, float* state, const float* actions, uint64_t mask, float* obs, float* rew, uint8_t* term, \
                        float* rew_sum, uint8_t* term_flag, int32_t* diag, unsigned long long* cycles
@@ -49,6 +53,8 @@ struct LaunchTable {
   // joint reaction wrenches, applied motor torques (dg_jointq.h)
   void (*joint_wrench)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const JwSelectors& sel, float* wrench, float* gws);
   void (*joint_effort)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, float* out, float* gws);
+  // link accelerations, IMU readings (dg_accelq.h)
+  void (*link_accel)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const LaSelectors& sel, float* out, float* gws);
 };
 // closest-points query (dg_closestq.h): one kernel for every mode -- it uses no workspace -- defined in the 64-lane query unit
 void l_closest(dim3 grid, hipStream_t st, DevScene sc, const float* table, int body_a, int link_a, int body_b, int link_b, float distance, int max_points, int no_cull,

@@ -456,6 +456,49 @@ int32_t dg_world_joint_wrench(dg_world* w, const float* state, int32_t body,
     const dg_joint_selector* selectors /* host [n] */, int32_t n, float* wrench /* [num_envs][n][6]: force3 torque3 */, void* stream);
 int32_t dg_world_joint_efforts(dg_world* w, const float* state, int32_t body, float* out /* [num_envs][n_links] */, void* stream);
 
+/* Link accelerations and IMU readings: how links ACCELERATE, and what an accelerometer and a gyro mounted on one read, every env at
+ * once.  pybullet has no such call and the reference no such addon; what env.sim.link_accelerations and the imu_sensor addon are
+ * built on.  The rules of the query entries above: device float32 arrays, one launch on `stream`, nothing allocated, freed or
+ * synchronised, the state is not written; on an error nothing is launched, outputs are untouched and dg_last_error names the entry.
+ *
+ * dg_world_link_accelerations  n sensor-frame selectors of ONE body, 1 <= n <= DG_LINK_ACCEL_MAX, as a HOST array copied into the
+ *                         kernel's arguments.  A selector names a frame S: `frame` the pybullet joint index (-1: the base), `com`
+ *                         0 the URDF link frame (what camera and lidar mount on) or 1 the link's inertial frame (as
+ *                         dg_world_link_states), and a mount pose `pos`, `quat` (xyzw, normalised by the entry) relative to it.
+ *                         Let L be the moving link S is rigidly attached to, (R_L, p_L, w, v, alpha, a) its pose and motion --
+ *                         accelerations (v_now - v_prev) / h with h the substep and v_prev the body's velocities at the start of
+ *                         the last substep (DG_BI_PREV_OFF), exactly as dg_world_joint_wrench forms them -- R_s, p_s the world
+ *                         pose of S, r = p_s - p_L and g the scene's gravity.  out [num_envs][n][DG_LA_STRIDE], columns DG_LA_*:
+ *                           DG_LA_LIN_ACC         a + alpha x r + w x (w x r), world axes
+ *                           DG_LA_ANG_ACC         alpha, world axes
+ *                           DG_LA_SPECIFIC_FORCE  R_s^T (lin_acc - g): what an accelerometer reads ((0, 0, +|g|) at rest and level)
+ *                           DG_LA_ANG_VEL         R_s^T w: what a gyro reads
+ *                           DG_LA_GRAVITY         R_s^T g / |g|, zeros when g = 0: the projected gravity direction
+ *                         No contact term and no narrow phase: contact, motor and external forces show through the motion, so a
+ *                         world without candidate pairs or without the contact impulse cache is taken.
+ *                         STALENESS follows dg_world_joint_wrench.  Nothing saves velocities on a teleport: after
+ *                         dg_world_reset_joint_state, dg_world_reset_base_state or a state written by the caller that changes a
+ *                         velocity, the reading carries the jump (v_new - v_prev) / h until the next step; the state of the last
+ *                         step handed in unchanged reads as before.  After dg_world_reset the accelerations are zero and
+ *                         specific_force = -R_s^T g.
+ *                         Bodies: a floating base with or without joints, a fixed base with joints.
+ *                         DG_ERR_ARG: NULL world, state, selectors or out; n out of range; a body out of range, frozen or WITHOUT
+ *                         SAVED VELOCITIES (the message names the remedy: builder.enable_joint_force_torque(body) at build time
+ *                         -- imu_sensor does -- or a compiled force_torque_sensor on the body; a fixed base without joints keeps
+ *                         none: its reading is the constant -g); a frame the body does not have; a mount quaternion of zero norm;
+ *                         a body whose pose and motion block (21 slots for the base and per link) does not fit the world's
+ *                         transient region. */
+#define DG_LINK_ACCEL_MAX 16
+enum { DG_LA_LIN_ACC = 0, DG_LA_ANG_ACC = 3, DG_LA_SPECIFIC_FORCE = 6, DG_LA_ANG_VEL = 9, DG_LA_GRAVITY = 12, DG_LA_STRIDE = 15 };
+typedef struct dg_accel_selector {
+  int32_t frame;   /* pybullet joint index of the body, -1: the base (the kernels see the global frame index) */
+  int32_t com;     /* 0: the URDF link frame, 1: the link's inertial frame */
+  float pos[3];    /* the mount: position in that frame */
+  float quat[4];   /* ... and orientation, xyzw */
+} dg_accel_selector;  /* 36 bytes */
+int32_t dg_world_link_accelerations(dg_world* w, const float* state, int32_t body,
+    const dg_accel_selector* selectors /* host [n] */, int32_t n, float* out /* [num_envs][n][15] */, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
