@@ -24,21 +24,24 @@
 
 using namespace dg;
 
-namespace dg {
-extern const LaunchTable g_launch_table_64, g_launch_table_32, g_launch_table_16, g_launch_table_8, g_launch_table_4, g_launch_table_1, g_launch_table_0, g_launch_table_g16;
-const LaunchTable& launch_table(int lanes) { return lanes == 64 ? g_launch_table_64 : lanes == 32 ? g_launch_table_32 : lanes == 16 ? g_launch_table_16 : lanes == 8 ? g_launch_table_8 : lanes == 4 ? g_launch_table_4 : lanes == 1 ? g_launch_table_1 : lanes == -16 ? g_launch_table_g16 : g_launch_table_0; }
-}  // namespace dg
-// the same kernels with the hull-hull contact manifold compiled in (dg_inst.hip -DDG_MANIFOLD: the headers in namespace dg_mf, the
-// same types member for member); no helper-wave form
-namespace dg_mf {
-extern const dg::LaunchTable g_launch_table_64, g_launch_table_32, g_launch_table_16, g_launch_table_8, g_launch_table_4, g_launch_table_1, g_launch_table_0, g_launch_table_g16;
-}
+// Every mode's table (dg_inst.hip), X(lanes, tag): in dg, and in dg_mf the same kernels with the hull-hull contact manifold compiled in
+// (-DDG_MANIFOLD: the headers in namespace dg_mf, the same types member for member -- both tables come from the one list of
+// dg_launch.h); no helper-wave form there.  The global-workspace mode comes last: an unknown `lanes` falls to it.
+#define DG_MODES(X) X(64, 64) X(32, 32) X(16, 16) X(8, 8) X(4, 4) X(1, 1) X(-16, g16) X(0, 0)
+#define DG_DECLARE(lanes, tag) namespace dg { extern const LaunchTable g_launch_table_##tag; } namespace dg_mf { extern const dg::LaunchTable g_launch_table_##tag; }
+DG_MODES(DG_DECLARE)
+#undef DG_DECLARE
 namespace dg {
 const LaunchTable& launch_table(int lanes, bool mf) {
-  namespace m = dg_mf;
-  if (!mf) return launch_table(lanes);
-  return lanes == 64 ? m::g_launch_table_64 : lanes == 32 ? m::g_launch_table_32 : lanes == 16 ? m::g_launch_table_16 : lanes == 8 ? m::g_launch_table_8 :
-         lanes == 4 ? m::g_launch_table_4 : lanes == 1 ? m::g_launch_table_1 : lanes == -16 ? m::g_launch_table_g16 : m::g_launch_table_0;
+  static const struct { int lanes; const LaunchTable *plain, *manifold; } rows[] = {
+#define DG_ROW(lanes, tag) {lanes, &g_launch_table_##tag, &dg_mf::g_launch_table_##tag},
+      DG_MODES(DG_ROW)
+#undef DG_ROW
+  };
+  constexpr int n = sizeof rows / sizeof *rows;
+  int r = 0;
+  while (r < n - 1 && rows[r].lanes != lanes) r++;
+  return mf ? *rows[r].manifold : *rows[r].plain;
 }
 }  // namespace dg
 
@@ -91,6 +94,65 @@ struct dg_world {
     (void)hipFree(d_gws); (void)hipFree(d_hull_ws); (void)hipFree(d_render_table); (void)hipFree(d_blob_i); (void)hipFree(d_blob_f); (void)hipFree(d_plan); (void)hipFree(d_init);
   }
 };
+
+// `frame` as the C-ABI takes it -- the body-local pybullet joint index -- to the global frame index the kernels use; -1: the body
+// has no such frame
+static int global_frame(const dg_world* w, int32_t body, int32_t frame) {
+  const int32_t* I = w->I.data(); const int32_t* FI = I + I[DG_H_OFF_FRAME_I]; int seen = 0;
+  for (int f = 0; f < w->sc.nfr; f++) if (FI[f * DG_FI_STRIDE + DG_FI_BODY] == body) { if (seen == frame) return f; seen++; }
+  return -1;
+}
+
+static dim3 grid_of(const dg_world* w) { const int per = envs_per_wave(w->lanes); return dim3((w->num_envs + per - 1) / per); }
+
+// The tail of every entry that launches a kernel of DG_QUERY_KERNELS: the world's device, the mode's launcher of `member` with the
+// world's scene and motor table, `state` and `args` -- the kernel's parameters after `state` -- and what the launch left behind.
+template <class M, class... A>
+static int launch_args(const dg_world* w, void* stream, M LaunchTable::*member, const float* state, const A&... args) {
+  DG_ON_DEVICE(w->device);
+  (launch_table(w->lanes, w->mf).*member)(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), args...);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
+}
+// ... for the kernels that end in the workspace pointer: every one but pose_kernel
+template <class M, class... A>
+static int launch(const dg_world* w, void* stream, M LaunchTable::*member, const float* state, const A&... args) {
+  return launch_args(w, stream, member, state, args..., w->d_gws);
+}
+// pose_kernel into `table`: the shape rows, the rows of the world's `ncam` cameras and of `nmount` mounts (body, global frame)
+static int launch_pose(const dg_world* w, void* stream, const float* state, int ncam, float* table, int nmount, int mbody, int mframe) {
+  return launch_args(w, stream, &LaunchTable::pose, state, ncam, w->d_CI, w->d_CF, table, w->d_gws, nmount, mbody, mframe);
+}
+
+// ------------------------------------------------------------------ refusals that several entries share
+// 0 or the error code, the message under the entry's name `what`; the entries older than the queries name none (nullptr)
+#define DG_WHAT(what) (what) ? (what) : "", (what) ? ": " : ""
+static const int32_t* body_row(const dg_world* w, int32_t body) { const int32_t* I = w->I.data(); return I + I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE; }
+static int body_check(const dg_world* w, int32_t body, const char* what) {
+  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "%s%sbody %d out of range", DG_WHAT(what), body);
+  return DG_OK;
+}
+// `frame` as the C-ABI takes it to the global frame index in *gf; a negative one is the base (-1).  False: the body has no such frame
+static bool frame_lookup(const dg_world* w, int32_t body, int32_t frame, int* gf) {
+  *gf = frame < 0 ? -1 : global_frame(w, body, frame);
+  return frame < 0 || *gf >= 0;
+}
+static int frame_check(const dg_world* w, int32_t body, int32_t frame, int* gf, const char* what) {
+  if (!frame_lookup(w, body, frame, gf)) return fail(DG_ERR_ARG, "%s%sbody %d has no frame %d", DG_WHAT(what), body, frame);
+  return DG_OK;
+}
+// a pass over the body would borrow `need` slots of the transient region, more than sc.tr_slots
+static int slots_refusal(const dg_world* w, int32_t body, int need, const char* what) {
+  return fail(DG_ERR_ARG, "%s: body %d needs %d workspace slots, the world's transient region has %d", what, body, need, w->sc.tr_slots);
+}
+// the contact readouts that report the solver's impulses
+static int impulse_cache_check(const dg_world* w, const char* what) {
+  if (w->sc.warm_off < 0)
+    return fail(DG_ERR_UNSUPPORTED, "%s: the world keeps no contact impulse cache (warmstart and warmstart_friction are 0, or the scene has no candidate pairs): "
+                                    "no forces to report", what);
+  return DG_OK;
+}
+#undef DG_WHAT
 
 extern "C" {
 
@@ -200,25 +262,13 @@ int32_t dg_world_init_state(dg_world* w, float* state, void* stream) {
   return DG_OK;
 }
 
-// `frame` as the C-ABI takes it -- the body-local pybullet joint index -- to the global frame index the kernels use; -1: the body
-// has no such frame
-static int global_frame(const dg_world* w, int32_t body, int32_t frame) {
-  const int32_t* I = w->I.data(); const int32_t* FI = I + I[DG_H_OFF_FRAME_I]; int seen = 0;
-  for (int f = 0; f < w->sc.nfr; f++) if (FI[f * DG_FI_STRIDE + DG_FI_BODY] == body) { if (seen == frame) return f; seen++; }
-  return -1;
-}
-
-static dim3 grid_of(const dg_world* w) { const int per = envs_per_wave(w->lanes); return dim3((w->num_envs + per - 1) / per); }
-
 int32_t dg_world_reset(dg_world* w, float* state, const uint8_t* mask, float* obs, void* stream) {
   if (!w || !state) return fail(DG_ERR_ARG, "null argument");
-  DG_ON_DEVICE(w->device);
   // four-wavefront scenes with the usual single hot-start step: the reset ops and that step run in the step kernel itself
   // (reset mode), the envs the mask does not name computing in their scratch workspace with stores off
-  if (w->par && w->sc.hot_start == 1 && !w->no_par_reset)
-    launch_table(w->lanes, w->mf).step_par(grid_of(w), w->lds_bytes, (hipStream_t)stream, false, w->sc, w->mt, state, nullptr, 0ull, obs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mask, 1);
-  else
-    launch_table(w->lanes, w->mf).reset(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, mask, obs, w->d_gws);
+  if (!(w->par && w->sc.hot_start == 1 && !w->no_par_reset)) return launch(w, stream, &LaunchTable::reset, state, mask, obs);
+  DG_ON_DEVICE(w->device);
+  launch_table(w->lanes, w->mf).step_par(grid_of(w), w->lds_bytes, (hipStream_t)stream, false, w->sc, w->mt, state, nullptr, 0ull, obs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mask, 1);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }
@@ -259,8 +309,7 @@ int32_t dg_world_render(dg_world* w, const float* state, int32_t camera, float* 
   if (!w || !state) return fail(DG_ERR_ARG, "null argument");
   if (camera < 0 || camera >= w->ncam) return fail(DG_ERR_ARG, "camera %d out of range (scene has %d)", camera, w->ncam);
   DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).pose(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), w->ncam, w->d_CI, w->d_CF, w->d_render_table, w->d_gws, 0, -1, -1);
-  HIP_TRY(hipGetLastError());
+  if (const int rc = launch_pose(w, stream, state, w->ncam, w->d_render_table, 0, -1, -1)) return rc;
   const int32_t* I = w->I.data(); const int32_t* ci = I + I[DG_H_OFF_CAMERA_I] + camera * DG_CI_STRIDE;
   // Rows per workgroup: a multiple of 8 (the tile height of render_kernel's wavefronts; 200-wide images: whole cache lines).
   // Every workgroup first builds its list of shapes, faces and vertices (phase A, a few microseconds of dependent loads),
@@ -276,16 +325,13 @@ int32_t dg_world_render(dg_world* w, const float* state, int32_t camera, float* 
   const int nbands = (H + band_rows - 1) / band_rows;
   const long long blocks = (long long)nbands * w->num_envs;  // the env index is folded into grid.x (grid.y stops at 65535)
   if (blocks > 0x7fffffffLL) return fail(DG_ERR_UNSUPPORTED, "render: %lld workgroups exceed the grid limit", blocks);
-  if (w->render_wpe == 1) {
-    hipLaunchKernelGGL(render_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w->sc, w->d_CI, w->d_CF, w->d_PLN, camera, w->ncam,
-                     (cfp)w->d_render_table, rgb, depth, seg, band_rows, nbands, w->render_diag);
-  } else if (w->render_wpe == 3) {
-    hipLaunchKernelGGL(render_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w->sc, w->d_CI, w->d_CF, w->d_PLN, camera, w->ncam,
-                     (cfp)w->d_render_table, rgb, depth, seg, band_rows, nbands, w->render_diag);
-  } else {
-    hipLaunchKernelGGL(render_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w->sc, w->d_CI, w->d_CF, w->d_PLN, camera, w->ncam,
-                     (cfp)w->d_render_table, rgb, depth, seg, band_rows, nbands, w->render_diag);
-  }
+  auto render = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w->sc, w->d_CI, w->d_CF, w->d_PLN, camera, w->ncam,
+                       (cfp)w->d_render_table, rgb, depth, seg, band_rows, nbands, w->render_diag);
+  };
+  if (w->render_wpe == 1) render(render_kernel<1>);
+  else if (w->render_wpe == 3) render(render_kernel<3>);
+  else render(render_kernel<2>);
   HIP_TRY(hipGetLastError());
   return DG_OK;
 }
@@ -308,15 +354,14 @@ int32_t dg_world_raycast(dg_world* w, const float* state, int32_t body, int32_t 
   if (skip_body < -1 || skip_body >= w->sc.nb) return fail(DG_ERR_ARG, "skip_body %d out of range", skip_body);
   if (body < 0 && frame != -1) return fail(DG_ERR_ARG, "frame %d given without a body", frame);
   if (frame < -1) return fail(DG_ERR_ARG, "frame %d out of range", frame);
-  int gf = -1;  // `frame` is the body-local pybullet joint index; the kernels use the global frame index
-  if (frame >= 0 && (gf = global_frame(w, body, frame)) < 0) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
+  int gf;
+  if (const int rc = frame_check(w, body, frame, &gf, nullptr)) return rc;
   // one workgroup per (env, chunk of rays): a wavefront per 64 rays, at most four of them
   const int threads = 64 * std::min(4, (n_rays + 63) / 64), nchunks = (n_rays + threads - 1) / threads;
   const long long blocks = (long long)nchunks * w->num_envs;  // the env index is folded into grid.x
   if (blocks > 0x7fffffffLL) return fail(DG_ERR_UNSUPPORTED, "raycast: %lld workgroups exceed the grid limit", blocks);
   DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).pose(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), 0, w->d_CI, w->d_CF, scratch, w->d_gws, 1, body, gf);
-  HIP_TRY(hipGetLastError());
+  if (const int rc = launch_pose(w, stream, state, 0, scratch, 1, body, gf)) return rc;
   const int words = w->sc.nsh * RY_STRIDE;
   if (words <= w->ray_lds_words)
     hipLaunchKernelGGL(raycast_kernel<true>, dim3((unsigned)blocks), dim3(threads), sizeof(float) * (size_t)words, (hipStream_t)stream, w->sc, w->d_PLN, (cfp)scratch, n_rays, nchunks,
@@ -353,6 +398,20 @@ int32_t dg_debug_render_counters(uint64_t* out16, int32_t reset) {
   return DG_OK;
 }
 
+// the device buffers of the two hull diagnostics below, freed on every way out: both hulls' points, the poses [n][24], the output
+// [n][out_floats] and the polytope workspace of the `blocks` wavefronts
+struct HullDebugBufs {
+  float *pts = nullptr, *poses = nullptr, *out = nullptr, *ws = nullptr; size_t blocks = 0;
+  ~HullDebugBufs() { (void)hipFree(pts); (void)hipFree(poses); (void)hipFree(out); (void)hipFree(ws); }
+};
+static int hull_debug_upload(HullDebugBufs& b, const float* pts_a, int na, const float* pts_b, int nb, const float* poses, int n, int out_floats) {
+  b.blocks = (size_t)((n + 63) / 64);
+  HIP_TRY(hipMalloc(&b.ws, sizeof(float) * b.blocks * (size_t)HH_WS_SLOTS * 64));
+  HIP_TRY(hipMalloc(&b.pts, sizeof(float) * 3 * (size_t)(na + nb))); HIP_TRY(hipMalloc(&b.poses, sizeof(float) * 24 * (size_t)n)); HIP_TRY(hipMalloc(&b.out, sizeof(float) * out_floats * (size_t)n));
+  HIP_TRY(hipMemcpy(b.pts, pts_a, sizeof(float) * 3 * (size_t)na, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(b.pts + 3 * na, pts_b, sizeof(float) * 3 * (size_t)nb, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b.poses, poses, sizeof(float) * 24 * (size_t)n, hipMemcpyHostToDevice));
+  return DG_OK;
+}
 // diagnostics: the hull-against-hull narrow phase (dg_hull.h) on its own, one pair of poses per lane -- tests/test_hull_contacts.py
 // compares it with the CPU checker and a brute-force Minkowski difference; host pointers; not part of the public header.
 // poses [n][24] = A: rotation (9, row-major), position (3); B: the same.  out [n][12] = witness on A, witness on B, normal from B
@@ -374,16 +433,11 @@ __global__ __launch_bounds__(64) void hull_pair_kernel(cfp pts, int na, int nb, 
 }
 int32_t dg_debug_hull_hull(const float* pts_a, int32_t na, const float* pts_b, int32_t nb, const float* poses, int32_t n, float max_dist, float* out11 /* [n][12] */) {
   if (!pts_a || !pts_b || !poses || !out11 || na < 1 || nb < 1 || na > 256 || nb > 256 || n < 1) return fail(DG_ERR_ARG, "dg_debug_hull_hull: bad argument");
-  struct Bufs { float *pts = nullptr, *poses = nullptr, *out = nullptr, *ws = nullptr;
-                ~Bufs() { (void)hipFree(pts); (void)hipFree(poses); (void)hipFree(out); (void)hipFree(ws); } } b;  // (freed on every way out)
-  float *&d_pts = b.pts, *&d_poses = b.poses, *&d_out = b.out, *&d_ws = b.ws; const size_t blocks = (size_t)((n + 63) / 64);
-  HIP_TRY(hipMalloc(&d_ws, sizeof(float) * blocks * (size_t)HH_WS_SLOTS * 64));
-  HIP_TRY(hipMalloc(&d_pts, sizeof(float) * 3 * (size_t)(na + nb))); HIP_TRY(hipMalloc(&d_poses, sizeof(float) * 24 * (size_t)n)); HIP_TRY(hipMalloc(&d_out, sizeof(float) * 12 * (size_t)n));
-  HIP_TRY(hipMemcpy(d_pts, pts_a, sizeof(float) * 3 * (size_t)na, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(d_pts + 3 * na, pts_b, sizeof(float) * 3 * (size_t)nb, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_poses, poses, sizeof(float) * 24 * (size_t)n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(hull_pair_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)0, (cfp)d_pts, na, nb, (const float*)d_poses, n, max_dist, d_out, d_ws);
+  HullDebugBufs b;
+  if (const int rc = hull_debug_upload(b, pts_a, na, pts_b, nb, poses, n, 12)) return rc;
+  hipLaunchKernelGGL(hull_pair_kernel, dim3((unsigned)b.blocks), dim3(64), 0, (hipStream_t)0, (cfp)b.pts, na, nb, (const float*)b.poses, n, max_dist, b.out, b.ws);
   HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out11, d_out, sizeof(float) * 12 * (size_t)n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out11, b.out, sizeof(float) * 12 * (size_t)n, hipMemcpyDeviceToHost));
   return DG_OK;
 }
 
@@ -428,14 +482,9 @@ int32_t dg_debug_hull_manifold(const float* pts_a, int32_t na, const float* pts_
                                float margin, float hull_margin, int32_t npts, float* out25 /* [n][25] */) {
   if (!pts_a || !pts_b || !poses || !out25 || na < 1 || nb < 1 || na > 256 || nb > 256 || n < 1 || npts < 1 || npts > 4)
     return fail(DG_ERR_ARG, "dg_debug_hull_manifold: bad argument");
-  struct Bufs { float *pts = nullptr, *poses = nullptr, *out = nullptr, *ws = nullptr;
-                ~Bufs() { (void)hipFree(pts); (void)hipFree(poses); (void)hipFree(out); (void)hipFree(ws); } } b;  // (freed on every way out)
-  const size_t blocks = (size_t)((n + 63) / 64);
-  HIP_TRY(hipMalloc(&b.ws, sizeof(float) * blocks * (size_t)HH_WS_SLOTS * 64));
-  HIP_TRY(hipMalloc(&b.pts, sizeof(float) * 3 * (size_t)(na + nb))); HIP_TRY(hipMalloc(&b.poses, sizeof(float) * 24 * (size_t)n)); HIP_TRY(hipMalloc(&b.out, sizeof(float) * 25 * (size_t)n));
-  HIP_TRY(hipMemcpy(b.pts, pts_a, sizeof(float) * 3 * (size_t)na, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(b.pts + 3 * na, pts_b, sizeof(float) * 3 * (size_t)nb, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(b.poses, poses, sizeof(float) * 24 * (size_t)n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(hull_manifold_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)0, (cfp)b.pts, na, nb, rad_a, rad_b, (const float*)b.poses, n,
+  HullDebugBufs b;
+  if (const int rc = hull_debug_upload(b, pts_a, na, pts_b, nb, poses, n, 25)) return rc;
+  hipLaunchKernelGGL(hull_manifold_kernel, dim3((unsigned)b.blocks), dim3(64), 0, (hipStream_t)0, (cfp)b.pts, na, nb, rad_a, rad_b, (const float*)b.poses, n,
                      margin, hull_margin, (int)npts, b.out, b.ws);
   HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out25, b.out, sizeof(float) * 25 * (size_t)n, hipMemcpyDeviceToHost));
@@ -446,21 +495,15 @@ int32_t dg_world_set_profile_buffer(dg_world* w, uint64_t* cycles) { if (!w) ret
 
 int32_t dg_world_observe(dg_world* w, const float* state, float* obs, float* rew, uint8_t* term, float* rew_sum, uint8_t* term_flag, void* stream) {
   if (!w || !state) return fail(DG_ERR_ARG, "null argument");
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).observe(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), obs, rew, term, rew_sum, term_flag, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::observe, state, obs, rew, term, rew_sum, term_flag);
 }
 
 int32_t dg_world_frame_state(dg_world* w, const float* state, int32_t body, int32_t frame, int32_t com, float* out, void* stream) {
   if (!w || !state || !out) return fail(DG_ERR_ARG, "null argument");
-  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "body %d out of range", body);
-  int gf = -1;  // `frame` is the body-local pybullet joint index; the kernels use the global frame index
-  if (frame >= 0 && (gf = global_frame(w, body, frame)) < 0) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).frame(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, gf, com, out, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  int gf;
+  if (const int rc = body_check(w, body, nullptr)) return rc;
+  if (const int rc = frame_check(w, body, frame, &gf, nullptr)) return rc;
+  return launch(w, stream, &LaunchTable::frame, state, body, gf, com, out);
 }
 
 int32_t dg_world_set_render_diag(dg_world* w, int32_t flags) {
@@ -472,103 +515,79 @@ int32_t dg_world_set_render_diag(dg_world* w, int32_t flags) {
 int32_t dg_world_apply_wrench(dg_world* w, float* state, int32_t body, int32_t frame, int32_t flags, const float* force, const float* pos,
                               const float* torque, void* stream) {
   if (!w || !state) return fail(DG_ERR_ARG, "null argument");
-  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "body %d out of range", body);
-  const int32_t* I = w->I.data();
-  if (I[I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE + DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "body %d is part of the frozen static world: it has no state to push on", body);
+  int gf;
+  if (const int rc = body_check(w, body, nullptr)) return rc;
+  if (body_row(w, body)[DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "body %d is part of the frozen static world: it has no state to push on", body);
   if (flags != DG_WRENCH_WORLD_FRAME && flags != DG_WRENCH_LINK_FRAME) return fail(DG_ERR_ARG, "flags must be DG_WRENCH_LINK_FRAME (1) or DG_WRENCH_WORLD_FRAME (2)");
-  int gf = -1;  // `frame` is the body-local pybullet joint index; the kernels use the global frame index
-  if (frame >= 0 && (gf = global_frame(w, body, frame)) < 0) return fail(DG_ERR_ARG, "body %d has no frame %d", body, frame);
+  if (const int rc = frame_check(w, body, frame, &gf, nullptr)) return rc;
   if (!force && !torque) return DG_OK;
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).wrench(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, gf, flags == DG_WRENCH_LINK_FRAME ? 1 : 0, force, pos, torque, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::wrench, state, body, gf, flags == DG_WRENCH_LINK_FRAME ? 1 : 0, force, pos, torque);
 }
 
 // ------------------------------------------------------------------ dynamics queries (dg_dynq.h)
 // the checks the five entries share: a fixed-base body with joints whose passes fit the transient region; 0 or the error code
 static int dynq_check(const dg_world* w, const void* state, int32_t body, int kind, const char* what) {
   if (!w || !state) return fail(DG_ERR_ARG, "%s: null argument", what);
-  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "%s: body %d out of range", what, body);
-  const int32_t* I = w->I.data(); const int32_t* B = I + I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE;
+  if (const int rc = body_check(w, body, what)) return rc;
+  const int32_t* B = body_row(w, body);
   if (B[DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "%s: body %d is part of the frozen static world: it has no joints", what, body);
   if (!(B[DG_BI_FLAGS] & DG_BODY_FIXED)) return fail(DG_ERR_ARG, "%s: body %d has a floating base; the dynamics queries take fixed-base bodies only", what, body);
   if (B[DG_BI_N_LINKS] < 1) return fail(DG_ERR_ARG, "%s: body %d has no joints", what, body);
-  if (kind >= 0 && dynq_slots(kind, B[DG_BI_N_LINKS]) > w->sc.tr_slots)
-    return fail(DG_ERR_ARG, "%s: body %d needs %d workspace slots, the world's transient region has %d", what, body, dynq_slots(kind, B[DG_BI_N_LINKS]), w->sc.tr_slots);
+  if (kind >= 0 && dynq_slots(kind, B[DG_BI_N_LINKS]) > w->sc.tr_slots) return slots_refusal(w, body, dynq_slots(kind, B[DG_BI_N_LINKS]), what);
   return DG_OK;
 }
 
 int32_t dg_world_joint_state(dg_world* w, const float* state, int32_t body, float* q_out, float* qd_out, void* stream) {
   if (const int rc = dynq_check(w, state, body, -1, "dg_world_joint_state")) return rc;
   if (!q_out && !qd_out) return DG_OK;
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).joint_state(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, q_out, qd_out, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::joint_state, state, body, q_out, qd_out);
 }
 
 int32_t dg_world_jacobian(dg_world* w, const float* state, int32_t body, int32_t frame, const float* local_pos, const float* q, float* jac_t, float* jac_r, void* stream) {
   if (const int rc = dynq_check(w, state, body, DQ_KIND_JACOBIAN, "dg_world_jacobian")) return rc;
   if (!local_pos) return fail(DG_ERR_ARG, "dg_world_jacobian: local_pos is NULL (three host floats)");
   if (frame < 0) return fail(DG_ERR_ARG, "dg_world_jacobian: frame %d out of range (the base of a fixed body does not move)", frame);
-  const int gf = global_frame(w, body, frame);
-  if (gf < 0) return fail(DG_ERR_ARG, "dg_world_jacobian: body %d has no frame %d", body, frame);
+  int gf;
+  if (const int rc = frame_check(w, body, frame, &gf, "dg_world_jacobian")) return rc;
   if (!jac_t && !jac_r) return DG_OK;
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).jacobian(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, gf, local_pos[0], local_pos[1], local_pos[2], q, jac_t, jac_r, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::jacobian, state, body, gf, local_pos[0], local_pos[1], local_pos[2], q, jac_t, jac_r);
 }
 
 int32_t dg_world_inverse_dynamics(dg_world* w, const float* state, int32_t body, const float* q, const float* qd, const float* qdd, float* tau, void* stream) {
   if (const int rc = dynq_check(w, state, body, DQ_KIND_ID, "dg_world_inverse_dynamics")) return rc;
   if (!tau) return fail(DG_ERR_ARG, "dg_world_inverse_dynamics: tau is NULL");
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).inverse_dynamics(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, q, qd, qdd, tau, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::inverse_dynamics, state, body, q, qd, qdd, tau);
 }
 
 int32_t dg_world_mass_matrix(dg_world* w, const float* state, int32_t body, const float* q, float* M, void* stream) {
   if (const int rc = dynq_check(w, state, body, DQ_KIND_MASS, "dg_world_mass_matrix")) return rc;
   if (!M) return fail(DG_ERR_ARG, "dg_world_mass_matrix: M is NULL");
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).mass_matrix(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, q, M, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::mass_matrix, state, body, q, M);
 }
 
 int32_t dg_world_apply_joint_torque(dg_world* w, float* state, int32_t body, const float* tau, void* stream) {
   if (const int rc = dynq_check(w, state, body, -1, "dg_world_apply_joint_torque")) return rc;
   if (!tau) return fail(DG_ERR_ARG, "dg_world_apply_joint_torque: tau is NULL");
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).joint_torque(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, tau, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::joint_torque, state, body, tau);
 }
 
 // ------------------------------------------------------------------ inverse-kinematics query, motor targets, joint reset (dg_ikq.h)
 int32_t dg_world_inverse_kinematics(dg_world* w, const float* state, int32_t body, int32_t frame, const float* target_pos, const float* target_orn,
                                     const float* lists, const float* q0, float* q_out, int32_t* iters_out, void* stream) {
   if (const int rc = dynq_check(w, state, body, -1, "dg_world_inverse_kinematics")) return rc;
-  const int n = w->I[w->I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE + DG_BI_N_LINKS];
-  if (ikq_slots(n) > w->sc.tr_slots)
-    return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: body %d needs %d workspace slots, the world's transient region has %d", body, ikq_slots(n), w->sc.tr_slots);
+  const int n = body_row(w, body)[DG_BI_N_LINKS];
+  if (ikq_slots(n) > w->sc.tr_slots) return slots_refusal(w, body, ikq_slots(n), "dg_world_inverse_kinematics");
   if (frame < 0) return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: frame %d out of range (the base of a fixed body does not move)", frame);
-  const int gf = global_frame(w, body, frame);
-  if (gf < 0) return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: body %d has no frame %d", body, frame);
+  int gf;
+  if (const int rc = frame_check(w, body, frame, &gf, "dg_world_inverse_kinematics")) return rc;
   if (!target_pos) return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: target_pos is NULL");
   if (!q_out) return fail(DG_ERR_ARG, "dg_world_inverse_kinematics: q_out is NULL");
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).ik_query(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, gf, target_pos, target_orn, lists, q0, q_out, iters_out, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::ik_query, state, body, gf, target_pos, target_orn, lists, q0, q_out, iters_out);
 }
 
 // a mask other than all ones cannot name the joints past the 64th
 static int joint_mask_check(const dg_world* w, int32_t body, uint64_t joint_mask, const char* what) {
-  const int n = w->I[w->I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE + DG_BI_N_LINKS];
+  const int n = body_row(w, body)[DG_BI_N_LINKS];
   if (n > 64 && joint_mask != ~0ull) return fail(DG_ERR_ARG, "%s: body %d has %d joints; a partial joint mask covers 64", what, body, n);
   return DG_OK;
 }
@@ -577,20 +596,14 @@ int32_t dg_world_set_joint_targets(dg_world* w, float* state, int32_t body, uint
   if (const int rc = dynq_check(w, state, body, -1, "dg_world_set_joint_targets")) return rc;
   if (const int rc = joint_mask_check(w, body, joint_mask, "dg_world_set_joint_targets")) return rc;
   if (!pos && !vel) return fail(DG_ERR_ARG, "dg_world_set_joint_targets: pos and vel are both NULL");
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).joint_targets(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, joint_mask, pos, vel, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::joint_targets, state, body, joint_mask, pos, vel);
 }
 
 int32_t dg_world_reset_joint_state(dg_world* w, float* state, int32_t body, uint64_t joint_mask, const float* q, const float* qd, const uint8_t* env_mask, void* stream) {
   if (const int rc = dynq_check(w, state, body, -1, "dg_world_reset_joint_state")) return rc;
   if (const int rc = joint_mask_check(w, body, joint_mask, "dg_world_reset_joint_state")) return rc;
   if (!q) return fail(DG_ERR_ARG, "dg_world_reset_joint_state: q is NULL");
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).joint_reset(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, joint_mask, q, qd, env_mask, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::joint_reset, state, body, joint_mask, q, qd, env_mask);
 }
 
 // ------------------------------------------------------------------ link states, base reset (dg_stateq.h)
@@ -600,15 +613,12 @@ int32_t dg_world_link_states(dg_world* w, const float* state, const int32_t* bod
   if (n < 1 || n > DG_LINK_STATES_MAX) return fail(DG_ERR_ARG, "dg_world_link_states: n must be 1 .. %d, got %d", (int)DG_LINK_STATES_MAX, n);
   LsSelectors sel; memset(&sel, 0, sizeof sel); sel.n = n;
   for (int k = 0; k < n; k++) {  // what dg_world_frame_state takes, selector by selector
-    const int body = bodies[k], frame = frames[k]; int gf = -1;
+    const int body = bodies[k], frame = frames[k]; int gf;
     if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_link_states: bodies[%d] = %d out of range", k, body);
-    if (frame >= 0 && (gf = global_frame(w, body, frame)) < 0) return fail(DG_ERR_ARG, "dg_world_link_states: body %d has no frame %d (selector %d)", body, frame, k);
+    if (!frame_lookup(w, body, frame, &gf)) return fail(DG_ERR_ARG, "dg_world_link_states: body %d has no frame %d (selector %d)", body, frame, k);
     sel.body[k] = body; sel.frame[k] = gf;
   }
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).link_states(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), sel, com, out, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::link_states, state, sel, com, out);
 }
 
 // A base can be moved only where the planner did not assume it stays at its load pose (scene.py: `frozen`, `anchored` -- static
@@ -617,10 +627,10 @@ int32_t dg_world_link_states(dg_world* w, const float* state, const int32_t* bod
 int32_t dg_world_reset_base_state(dg_world* w, float* state, int32_t body, const float* pos, const float* orn, const float* lin_vel, const float* ang_vel,
                                   const uint8_t* env_mask, void* stream) {
   if (!w || !state) return fail(DG_ERR_ARG, "dg_world_reset_base_state: null argument");
-  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_reset_base_state: body %d out of range", body);
+  if (const int rc = body_check(w, body, "dg_world_reset_base_state")) return rc;
   if ((pos == nullptr) != (orn == nullptr)) return fail(DG_ERR_ARG, "dg_world_reset_base_state: pos and orn go together (both or neither)");
   if (!pos && !lin_vel && !ang_vel) return fail(DG_ERR_ARG, "dg_world_reset_base_state: nothing to write (pos, orn, lin_vel and ang_vel are all NULL)");
-  const int32_t* I = w->I.data(); const int flags = I[I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE + DG_BI_FLAGS];
+  const int32_t* I = w->I.data(); const int flags = body_row(w, body)[DG_BI_FLAGS];
   if (flags & DG_BODY_FIXED) {
     bool respawned = false; const int32_t* OI = I + I[DG_H_OFF_OP_I];
     for (int op = 0; op < w->sc.nops; op++) respawned = respawned || (OI[op * DG_OI_STRIDE + DG_OI_CODE] == DG_OP_RESPAWN && OI[op * DG_OI_STRIDE + DG_OI_BODY] == body);
@@ -629,10 +639,7 @@ int32_t dg_world_reset_base_state(dg_world* w, float* state, int32_t body, const
                               "(zero ranges will do) to make its base movable", body);
     if (lin_vel || ang_vel) return fail(DG_ERR_ARG, "dg_world_reset_base_state: body %d has a fixed base: it takes a pose, no velocity", body);
   }
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).reset_base(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, state, body, pos, orn, lin_vel, ang_vel, env_mask, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::reset_base, state, body, pos, orn, lin_vel, ang_vel, env_mask);
 }
 
 // ------------------------------------------------------------------ contact query (dg_contactq.h)
@@ -661,15 +668,9 @@ int32_t dg_world_contacts(dg_world* w, const float* state, int32_t body_a, int32
   if (!count) return fail(DG_ERR_ARG, "dg_world_contacts: count is NULL (ids, geom and force may be)");
   if (const int rc = contact_filter_check(w, body_a, link_a, "a")) return rc;
   if (const int rc = contact_filter_check(w, body_b, link_b, "b")) return rc;
-  if (force && w->sc.warm_off < 0)
-    return fail(DG_ERR_UNSUPPORTED, "dg_world_contacts: the world keeps no contact impulse cache (warmstart and warmstart_friction are 0, or the scene has no "
-                                    "candidate pairs): no forces to report");
-  DG_ON_DEVICE(w->device);
+  if (force) if (const int rc = impulse_cache_check(w, "dg_world_contacts")) return rc;
   // the grid and block of reset_kernel: one wavefront per workgroup, as many workgroups as the step has (dg_contactq.h, Workspace)
-  launch_table(w->lanes, w->mf).contacts(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body_a, link_a, body_b, link_b,
-                                         count, ids, geom, force, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::contact_query, state, body_a, link_a, body_b, link_b, count, ids, geom, force);
 }
 
 // ------------------------------------------------------------------ contact forces (dg_contactf.h)
@@ -679,15 +680,9 @@ int32_t dg_world_contact_forces(dg_world* w, const float* state, int32_t body_a,
   if (!count) return fail(DG_ERR_ARG, "dg_world_contact_forces: count is NULL (ids and forces may be)");
   if (const int rc = contact_filter_check(w, body_a, link_a, "a", "dg_world_contact_forces")) return rc;
   if (const int rc = contact_filter_check(w, body_b, link_b, "b", "dg_world_contact_forces")) return rc;
-  if (w->sc.warm_off < 0)
-    return fail(DG_ERR_UNSUPPORTED, "dg_world_contact_forces: the world keeps no contact impulse cache (warmstart and warmstart_friction are 0, or the scene has "
-                                    "no candidate pairs): no forces to report");
-  DG_ON_DEVICE(w->device);
+  if (const int rc = impulse_cache_check(w, "dg_world_contact_forces")) return rc;
   // the grid and block of reset_kernel, as dg_world_contacts (dg_contactq.h, Workspace)
-  launch_table(w->lanes, w->mf).contact_forces(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body_a, link_a, body_b, link_b,
-                                               count, ids, forces, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::contact_force, state, body_a, link_a, body_b, link_b, count, ids, forces);
 }
 
 int32_t dg_world_net_contact_wrench(dg_world* w, const float* state, int32_t body, const int32_t* links, int32_t n, int32_t body_b, int32_t link_b,
@@ -695,7 +690,7 @@ int32_t dg_world_net_contact_wrench(dg_world* w, const float* state, int32_t bod
   if (!w || !state) return fail(DG_ERR_ARG, "dg_world_net_contact_wrench: null argument");
   if (!links || !wrench) return fail(DG_ERR_ARG, "dg_world_net_contact_wrench: links or wrench is NULL (ncontacts may be)");
   if (n < 1 || n > DG_CONTACT_MAX_LINKS) return fail(DG_ERR_ARG, "dg_world_net_contact_wrench: n must be 1 .. %d, got %d", (int)DG_CONTACT_MAX_LINKS, n);
-  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_net_contact_wrench: body %d out of range", body);
+  if (const int rc = body_check(w, body, "dg_world_net_contact_wrench")) return rc;
   CfSelectors sel; memset(&sel, 0, sizeof sel); sel.n = n;
   for (int s = 0; s < n; s++) {  // DG_CONTACT_ANY or a frame of the body: the moment needs the link's inertial frame
     const int link = links[s]; int gf = -1;
@@ -704,14 +699,8 @@ int32_t dg_world_net_contact_wrench(dg_world* w, const float* state, int32_t bod
     sel.link[s] = link; sel.frame[s] = gf;
   }
   if (const int rc = contact_filter_check(w, body_b, link_b, "b", "dg_world_net_contact_wrench")) return rc;
-  if (w->sc.warm_off < 0)
-    return fail(DG_ERR_UNSUPPORTED, "dg_world_net_contact_wrench: the world keeps no contact impulse cache (warmstart and warmstart_friction are 0, or the scene "
-                                    "has no candidate pairs): no forces to report");
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).net_contact_wrench(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, sel, body_b, link_b,
-                                                   wrench, ncontacts, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  if (const int rc = impulse_cache_check(w, "dg_world_net_contact_wrench")) return rc;
+  return launch(w, stream, &LaunchTable::net_contact_wrench, state, body, sel, body_b, link_b, wrench, ncontacts);
 }
 
 // ------------------------------------------------------------------ joint reaction wrenches, applied motor torques (dg_jointq.h)
@@ -719,8 +708,8 @@ int32_t dg_world_joint_wrench(dg_world* w, const float* state, int32_t body, con
   if (!w || !state) return fail(DG_ERR_ARG, "dg_world_joint_wrench: null argument");
   if (!selectors || !wrench) return fail(DG_ERR_ARG, "dg_world_joint_wrench: selectors or wrench is NULL");
   if (n < 1 || n > DG_JOINT_WRENCH_MAX) return fail(DG_ERR_ARG, "dg_world_joint_wrench: n must be 1 .. %d, got %d", (int)DG_JOINT_WRENCH_MAX, n);
-  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d out of range", body);
-  const int32_t* I = w->I.data(); const int32_t* B = I + I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE;
+  if (const int rc = body_check(w, body, "dg_world_joint_wrench")) return rc;
+  const int32_t* I = w->I.data(); const int32_t* B = body_row(w, body);
   if (B[DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d is part of the frozen static world: it has no joints", body);
   if (B[DG_BI_PREV_OFF] < 0)
     return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d keeps no saved velocities; call builder.enable_joint_force_torque(body) while the scene is built "
@@ -728,12 +717,11 @@ int32_t dg_world_joint_wrench(dg_world* w, const float* state, int32_t body, con
   const int nl = B[DG_BI_N_LINKS]; int nfr = 0;
   for (int f = 0; f < w->sc.nfr; f++) nfr += I[I[DG_H_OFF_FRAME_I] + f * DG_FI_STRIDE + DG_FI_BODY] == body;
   if (nl > 64 || nfr > 64) return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d has %d links and %d frames; the selectors' masks cover 64", body, nl, nfr);
-  if (jointq_slots(nl) > w->sc.tr_slots)
-    return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d needs %d workspace slots, the world's transient region has %d", body, jointq_slots(nl), w->sc.tr_slots);
+  if (jointq_slots(nl) > w->sc.tr_slots) return slots_refusal(w, body, jointq_slots(nl), "dg_world_joint_wrench");
   JwSelectors sel; memset(&sel, 0, sizeof sel); sel.n = n;
   for (int s = 0; s < n; s++) {
-    const dg_joint_selector& js = selectors[s]; int gf = -1;
-    if (js.frame < 0 || (gf = global_frame(w, body, js.frame)) < 0) return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d has no frame %d (selector %d)", body, js.frame, s);
+    const dg_joint_selector& js = selectors[s]; int gf;
+    if (js.frame < 0 || !frame_lookup(w, body, js.frame, &gf)) return fail(DG_ERR_ARG, "dg_world_joint_wrench: body %d has no frame %d (selector %d)", body, js.frame, s);
     if ((nl < 64 && (js.link_mask >> nl)) || (nfr < 64 && (js.frame_mask >> nfr)))
       return fail(DG_ERR_ARG, "dg_world_joint_wrench: selector %d names a link or frame past the body's %d links and %d frames", s, nl, nfr);
     if ((js.flags & DG_FT_WHOLE_LINK) && I[I[DG_H_OFF_FRAME_I] + gf * DG_FI_STRIDE + DG_FI_LINK] < 0)
@@ -743,23 +731,17 @@ int32_t dg_world_joint_wrench(dg_world* w, const float* state, int32_t body, con
   if (w->sc.npairs > 0 && w->sc.warm_off < 0)
     return fail(DG_ERR_UNSUPPORTED, "dg_world_joint_wrench: the world keeps no contact impulse cache (warmstart and warmstart_friction are 0): no contact forces "
                                     "to take off the child side");
-  DG_ON_DEVICE(w->device);
   // the grid and block of reset_kernel, as dg_world_contacts (dg_contactq.h, Workspace)
-  launch_table(w->lanes, w->mf).joint_wrench(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, sel, wrench, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::joint_wrench, state, body, sel, wrench);
 }
 
 int32_t dg_world_joint_efforts(dg_world* w, const float* state, int32_t body, float* out, void* stream) {
   if (!w || !state || !out) return fail(DG_ERR_ARG, "dg_world_joint_efforts: null argument");
-  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_joint_efforts: body %d out of range", body);
-  const int32_t* I = w->I.data(); const int32_t* B = I + I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE;
+  if (const int rc = body_check(w, body, "dg_world_joint_efforts")) return rc;
+  const int32_t* B = body_row(w, body);
   if (B[DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "dg_world_joint_efforts: body %d is part of the frozen static world: it has no joints", body);
   if (B[DG_BI_N_LINKS] < 1) return fail(DG_ERR_ARG, "dg_world_joint_efforts: body %d has no joints", body);
-  DG_ON_DEVICE(w->device);
-  launch_table(w->lanes, w->mf).joint_effort(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, out, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::joint_effort, state, body, out);
 }
 
 // ------------------------------------------------------------------ link accelerations, IMU readings (dg_accelq.h)
@@ -767,19 +749,18 @@ int32_t dg_world_link_accelerations(dg_world* w, const float* state, int32_t bod
   if (!w || !state) return fail(DG_ERR_ARG, "dg_world_link_accelerations: null argument");
   if (!selectors || !out) return fail(DG_ERR_ARG, "dg_world_link_accelerations: selectors or out is NULL");
   if (n < 1 || n > DG_LINK_ACCEL_MAX) return fail(DG_ERR_ARG, "dg_world_link_accelerations: n must be 1 .. %d, got %d", (int)DG_LINK_ACCEL_MAX, n);
-  if (body < 0 || body >= w->sc.nb) return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d out of range", body);
-  const int32_t* I = w->I.data(); const int32_t* B = I + I[DG_H_OFF_BODY_I] + body * DG_BI_STRIDE;
+  if (const int rc = body_check(w, body, "dg_world_link_accelerations")) return rc;
+  const int32_t* B = body_row(w, body);
   if (B[DG_BI_FLAGS] & DG_BODY_FROZEN) return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d is part of the frozen static world: it never moves", body);
   if (B[DG_BI_PREV_OFF] < 0)
     return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d keeps no saved velocities; call builder.enable_joint_force_torque(body) while the scene is built "
                             "(imu_sensor does), or put a compiled force_torque_sensor on the body; a fixed base without joints keeps none", body);
   const int nl = B[DG_BI_N_LINKS];
-  if (jointq_slots(nl) > w->sc.tr_slots)
-    return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d needs %d workspace slots, the world's transient region has %d", body, jointq_slots(nl), w->sc.tr_slots);
+  if (jointq_slots(nl) > w->sc.tr_slots) return slots_refusal(w, body, jointq_slots(nl), "dg_world_link_accelerations");
   LaSelectors sel; memset(&sel, 0, sizeof sel); sel.n = n;
   for (int s = 0; s < n; s++) {
-    const dg_accel_selector& as = selectors[s]; int gf = -1;
-    if (as.frame < -1 || (as.frame >= 0 && (gf = global_frame(w, body, as.frame)) < 0))
+    const dg_accel_selector& as = selectors[s]; int gf;
+    if (as.frame < -1 || !frame_lookup(w, body, as.frame, &gf))
       return fail(DG_ERR_ARG, "dg_world_link_accelerations: body %d has no frame %d (selector %d)", body, as.frame, s);
     const double qn = std::sqrt((double)as.quat[0] * as.quat[0] + (double)as.quat[1] * as.quat[1] + (double)as.quat[2] * as.quat[2] + (double)as.quat[3] * as.quat[3]);
     if (!(qn > 0.0) || !std::isfinite(qn)) return fail(DG_ERR_ARG, "dg_world_link_accelerations: the mount quaternion of selector %d has zero norm", s);
@@ -788,11 +769,8 @@ int32_t dg_world_link_accelerations(dg_world* w, const float* state, int32_t bod
   }
   const double gn = std::sqrt((double)w->sc.gx * w->sc.gx + (double)w->sc.gy * w->sc.gy + (double)w->sc.gz * w->sc.gz);
   if (gn > 0.0) { sel.ghat[0] = (float)(w->sc.gx / gn); sel.ghat[1] = (float)(w->sc.gy / gn); sel.ghat[2] = (float)(w->sc.gz / gn); }
-  DG_ON_DEVICE(w->device);
   // the grid and block of reset_kernel, as dg_world_joint_wrench
-  launch_table(w->lanes, w->mf).link_accel(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), body, sel, out, w->d_gws);
-  HIP_TRY(hipGetLastError());
-  return DG_OK;
+  return launch(w, stream, &LaunchTable::link_accel, state, body, sel, out);
 }
 
 // ------------------------------------------------------------------ closest-points query (dg_closestq.h)
@@ -818,8 +796,7 @@ int32_t dg_world_closest(dg_world* w, const float* state, int32_t body_a, int32_
   if (max_points > 0 && !ids && !geom) return fail(DG_ERR_ARG, "dg_world_closest: max_points %d with ids and geom both NULL", max_points);
   DG_ON_DEVICE(w->device);
   // the shape poses in the world's own workspace mode, then one wavefront per 64 envs: the grid the polytope workspace is sized for
-  launch_table(w->lanes, w->mf).pose(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), 0, w->d_CI, w->d_CF, scratch, w->d_gws, 0, -1, -1);
-  HIP_TRY(hipGetLastError());
+  if (const int rc = launch_pose(w, stream, state, 0, scratch, 0, -1, -1)) return rc;
   l_closest(dim3((unsigned)((w->num_envs + 63) / 64)), (hipStream_t)stream, w->sc, scratch, body_a, link_a, body_b, link_b, distance, max_points, w->closest_no_cull,
             scratch + closest_table_floats(w), count, ids, geom, nearest_ids, nearest_geom);
   HIP_TRY(hipGetLastError());

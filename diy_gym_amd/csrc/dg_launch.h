@@ -1,5 +1,6 @@
-// dg_launch.h -- host-side launch table: one set of wrappers per envs-per-wavefront mode, each defined in its own
+// dg_launch.h -- host-side launch table: one table of launchers per envs-per-wavefront mode, each defined in its own
 // translation unit (dg_inst.hip compiled with -DDG_LANES=... -DDG_PART=...), so the library builds in parallel.
+// DG_QUERY_KERNELS below is the one list of the one-wavefront kernels: table, launchers and LDS attributes are made from it.
 #pragma once
 #include "dg_kernels.h"
 
@@ -22,43 +23,50 @@ struct LaSelectors { int32_t n; float ghat[3]; dg_accel_selector s[DG_LINK_ACCEL
 
 #define DG_STEP_PARAMS DevScene sc, MotorTable mt, float* state, const float* actions, uint64_t mask, float* obs, float* rew, uint8_t* term, \
                        float* rew_sum, uint8_t* term_flag, int32_t* diag, unsigned long long* cycles
+// The one-wavefront kernels, one line each: X(name, the parameters of name_kernel<LANES> after `DevScene sc, MotorTable mt, float* state`).
+// The list makes the members of LaunchTable, their launchers, the LDS attribute of each kernel and the slots of each mode's table
+// (dg_inst.hip); a *Selectors struct goes by reference into the launcher and by value into the kernel.
+#define DG_QUERY_KERNELS(X) \
+  X(reset, const uint8_t* mask, float* obs, float* gws) \
+  X(observe, float* obs, float* rew, uint8_t* term, float* rew_sum, uint8_t* term_flag, float* gws) \
+  X(frame, int body, int frame, int com, float* out, float* gws) \
+  X(wrench, int body, int frame, int link_frame, const float* force, const float* pos, const float* torque, float* gws) \
+  X(pose, int ncam, cip CI, cfp CF, float* table, float* gws, int nmount, int mbody, int mframe) \
+  /* dynamics queries (dg_dynq.h) */ \
+  X(joint_state, int body, float* q_out, float* qd_out, float* gws) \
+  X(joint_torque, int body, const float* tau, float* gws) \
+  X(jacobian, int body, int frame, float lx, float ly, float lz, const float* q, float* jac_t, float* jac_r, float* gws) \
+  X(inverse_dynamics, int body, const float* q, const float* qd, const float* qdd, float* tau, float* gws) \
+  X(mass_matrix, int body, const float* q, float* M, float* gws) \
+  /* inverse-kinematics query, motor targets, joint reset (dg_ikq.h) */ \
+  X(ik_query, int body, int frame, const float* target_pos, const float* target_orn, const float* lists, const float* q0, float* q_out, int32_t* iters_out, float* gws) \
+  X(joint_targets, int body, uint64_t joint_mask, const float* pos, const float* vel, float* gws) \
+  X(joint_reset, int body, uint64_t joint_mask, const float* q, const float* qd, const uint8_t* env_mask, float* gws) \
+  /* contact query (dg_contactq.h), contact forces (dg_contactf.h) */ \
+  X(contact_query, int body_a, int link_a, int body_b, int link_b, int32_t* count, int32_t* ids, float* geom, float* force, float* gws) \
+  X(contact_force, int body_a, int link_a, int body_b, int link_b, int32_t* count, int32_t* ids, float* out, float* gws) \
+  X(net_contact_wrench, int body, const CfSelectors& sel, int body_b, int link_b, float* wrench, int32_t* ncontacts, float* gws) \
+  /* link states, base reset (dg_stateq.h) */ \
+  X(link_states, const LsSelectors& sel, int com, float* out, float* gws) \
+  X(reset_base, int body, const float* pos, const float* orn, const float* lin_vel, const float* ang_vel, const uint8_t* env_mask, float* gws) \
+  /* joint reaction wrenches, applied motor torques (dg_jointq.h) */ \
+  X(joint_wrench, int body, const JwSelectors& sel, float* wrench, float* gws) \
+  X(joint_effort, int body, float* out, float* gws) \
+  /* link accelerations, IMU readings (dg_accelq.h) */ \
+  X(link_accel, int body, const LaSelectors& sel, float* out, float* gws)
+
 struct LaunchTable {
   bool has_prof;
   hipError_t (*prepare)(int lds_bytes);
   void (*step)(dim3 grid, int lds, hipStream_t st, bool prof, DG_STEP_PARAMS, float* gws);
   void (*step_par)(dim3 grid, int lds, hipStream_t st, bool prof, DG_STEP_PARAMS, const uint8_t* reset_mask, int reset_mode);  // reset_mode 1: masked reset + one hot-start step (mask NULL = every env)
-  void (*reset)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, const uint8_t* mask, float* obs, float* gws);
-  void (*observe)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, float* obs, float* rew, uint8_t* term, float* rew_sum, uint8_t* term_flag, float* gws);
-  void (*frame)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, int com, float* out, float* gws);
-  void (*wrench)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, int link_frame, const float* force, const float* pos, const float* torque, float* gws);
-  void (*pose)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int ncam, cip CI, cfp CF, float* table, float* gws, int nmount, int mbody, int mframe);
-  // dynamics queries (dg_dynq.h)
-  void (*joint_state)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, float* q_out, float* qd_out, float* gws);
-  void (*joint_torque)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* tau, float* gws);
-  void (*jacobian)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, float lx, float ly, float lz, const float* q, float* jac_t, float* jac_r, float* gws);
-  void (*inverse_dynamics)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* q, const float* qd, const float* qdd, float* tau, float* gws);
-  void (*mass_matrix)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* q, float* M, float* gws);
-  // inverse-kinematics query, motor targets, joint reset (dg_ikq.h)
-  void (*ik_query)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, int frame, const float* target_pos, const float* target_orn, const float* lists, const float* q0, float* q_out, int32_t* iters_out, float* gws);
-  void (*joint_targets)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, uint64_t joint_mask, const float* pos, const float* vel, float* gws);
-  void (*joint_reset)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, uint64_t joint_mask, const float* q, const float* qd, const uint8_t* env_mask, float* gws);
-  // contact query (dg_contactq.h)
-  void (*contacts)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body_a, int link_a, int body_b, int link_b, int32_t* count, int32_t* ids, float* geom, float* force, float* gws);
-  // contact forces (dg_contactf.h)
-  void (*contact_forces)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body_a, int link_a, int body_b, int link_b, int32_t* count, int32_t* ids, float* out, float* gws);
-  void (*net_contact_wrench)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const CfSelectors& sel, int body_b, int link_b, float* wrench, int32_t* ncontacts, float* gws);
-  // link states, base reset (dg_stateq.h)
-  void (*link_states)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, const LsSelectors& sel, int com, float* out, float* gws);
-  void (*reset_base)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const float* pos, const float* orn, const float* lin_vel, const float* ang_vel, const uint8_t* env_mask, float* gws);
-  // joint reaction wrenches, applied motor torques (dg_jointq.h)
-  void (*joint_wrench)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const JwSelectors& sel, float* wrench, float* gws);
-  void (*joint_effort)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, float* out, float* gws);
-  // link accelerations, IMU readings (dg_accelq.h)
-  void (*link_accel)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, int body, const LaSelectors& sel, float* out, float* gws);
+#define DG_MEMBER(name, ...) void (*name)(dim3 grid, int lds, hipStream_t st, DevScene sc, MotorTable mt, float* state, __VA_ARGS__);
+  DG_QUERY_KERNELS(DG_MEMBER)
+#undef DG_MEMBER
 };
 // closest-points query (dg_closestq.h): one kernel for every mode -- it uses no workspace -- defined in the 64-lane query unit
 void l_closest(dim3 grid, hipStream_t st, DevScene sc, const float* table, int body_a, int link_a, int body_b, int link_b, float distance, int max_points, int no_cull,
                float* hull_ws, int32_t* count, int32_t* ids, float* geom, int32_t* nearest_ids, float* nearest_geom);
-const LaunchTable& launch_table(int lanes);  // lanes in {64, 32, 16, 8, 4, 1, 0, -16}
+const LaunchTable& launch_table(int lanes, bool mf);  // lanes in {64, 32, 16, 8, 4, 1, 0, -16}; mf: the kernels with the hull-hull manifold
 
 }  // namespace dg
