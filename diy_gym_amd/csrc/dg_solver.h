@@ -1906,7 +1906,9 @@ DGD bool split_decide_follow(const Lane<LANES>& ln, unsigned my_limit_bits, bool
 }
 
 // ---- register-chain sweeps of the helper-wave kernel, one (env, arm) per lane ------------------------------------
-// When a substep has no contact, the rows of the two register-chain bodies share no unknown; the only coupling is
+// For substeps in which some env of the workgroup has a contact (a workgroup without one takes fused_free_halves
+// below, which needs none of the LDS staging described here).  In an env without a contact the rows of the two
+// register-chain bodies share no unknown; the only coupling is
 // the per-env residual that decides the early-out.  Wavefront w (0 = main, 1 = helper) sweeps BOTH arms of the envs
 // [32 w, 32 w + 32) of the workgroup: lane l holds arm (l >> 5) of env 32 w + (l & 31), so the two residuals of an env
 // sit in lanes l and l ^ 32 of the same wavefront and are combined with one v_permlane32_swap -- no LDS round trip,
@@ -2082,10 +2084,136 @@ DGD void pgs_reg_halves(const Lane<LANES>& ln, int wave) {
   if (half == 0) W(split_slots(sc)) = (float)iters_done;  // for the diagnostics column, read by the main wave after the barrier
 }
 
+// ---- contact-free substep of the helper-wave kernel: rows, sweeps and integration in one lane mapping -------------
+// Is this substep of the workgroup free of contacts, and the scene one the fused path below covers (split sweeps, two
+// six-joint register chains, no fixed constraint)?  Called after B2 by all four wavefronts: the narrow phase has left
+// its contact counts in LDS before B2 and every wavefront reads the same 64 of them, so all four reach the same
+// verdict without a barrier.
+template <int LANES>
+DGD bool substep_contact_free(const Lane<LANES>& ln) {
+  const DevScene& sc = ln.sc;
+  if (sc.split_pgs <= 0 || sc.ncons > 0) return false;
+  if (ln.bi(sc.reg_body[0])[DG_BI_N_LINKS] != 6 || ln.bi(sc.helper_body)[DG_BI_N_LINKS] != 6) return false;
+  float cnt = ln.L(sc.cont_off);
+  if (sc.coll_split) cnt = fmaxf(cnt, ln.L(sc.cont2_off));
+  return !__any(cnt > 0.f);
+}
+// Everything between B2 and B3 for the two arms of such a substep, in the mapping of pgs_reg_halves: wavefront w
+// (0 = main, 1 = helper), lane l serves arm (l >> 5) of env 32 w + (l & 31).  The lane loads its arm's joint state and
+// M^-1 once, forms the motor and limit rows in registers (the expressions of setup_link_rows), runs the motor guess and
+// the sweeps (those of pgs_reg_halves without contact rows), and integrates its six joints (the joint loop of
+// integrate_body) -- no MR_* slot, no velocity change and no impulse goes through LDS, the joint state crosses global
+// memory once, and the barriers Bq and Bs are not needed.  Half of the lanes read joint velocities the OTHER wavefront's
+// dynamics stored before B2, and store positions the other wavefront's kinematics read after B3.
+// Stores are predicated on the lane's OWN env: bit `el` of the wavefront's `valid` mask (every wavefront sees the same
+// 64 envs), which is `exists` in the step kernel and `exists && reset_mask` in the reset kernel.
+template <int LANES, bool PROF>
+DGD void fused_free_halves(const Lane<LANES>& ln, int wave, Prof<PROF>& prof) {
+  constexpr int RN = 6;
+  const DevScene& sc = ln.sc; const float h = sc.h, lerp = sc.HF[DG_HF_LIMIT_ERP], vmax = sc.HF[DG_HF_MAX_COORD_VEL];
+  const float thr_abs = sqrtf(sc.HF[DG_HF_RESIDUAL_THRESHOLD]);
+  // The lane index is made opaque: everything below that is selected by `half` from launch constants (state offsets, gains,
+  // limits: ~40 registers) would otherwise be hoisted out of the substep loop and stay live through the dynamics, in a
+  // kernel at its register limit.  It costs no instruction.
+  int lane = threadIdx.x & 63; asm volatile("" : "+v"(lane));
+  const int half = lane >> 5, el = (lane & 31) + 32 * wave;
+  float* const col = ln.lds - (threadIdx.x & 63) + el;  // this lane's ENV column of the workspace
+  const int envl = (int)blockIdx.x * 64 + el; const bool exists = envl < sc.num_envs;
+  const bool store = (__ballot(ln.valid) >> el) & 1ull;
+  float* const st = ln.st - ln.env + (exists ? envl : sc.num_envs - 1);  // this lane's ENV column of the state
+  const size_t stride = sc.stride;
+  const int b0 = sc.reg_body[0], b1 = sc.helper_body;
+  const int f0 = ln.bi(b0)[DG_BI_FIRST_LINK], f1 = ln.bi(b1)[DG_BI_FIRST_LINK];
+  const int mvo = half ? ln.plb(b1)[PLB_MINV] : ln.plb(b0)[PLB_MINV];
+  const float* const cm = col + (size_t)mvo * 64;
+  int lo[RN]; float q[RN], qd[RN], tp[RN], tv[RN];
+#pragma unroll
+  for (int i = 0; i < RN; i++) {  // every state load before the first use
+    const int lo0 = ln.li(f0 + i)[DG_LI_STATE_OFF], lo1 = ln.li(f1 + i)[DG_LI_STATE_OFF]; lo[i] = half ? lo1 : lo0;
+    q[i] = st[(lo[i] + DG_LS_Q) * stride]; qd[i] = st[(lo[i] + DG_LS_QD) * stride];
+    tp[i] = st[(lo[i] + DG_LS_TARGET_POS) * stride]; tv[i] = st[(lo[i] + DG_LS_TARGET_VEL) * stride];
+  }
+  float rM[RN * RN], rdv[RN], rb[RN], racc[RN], rdi[RN], rdg[RN], smax[RN], lb[2][RN], la[2][RN];
+#pragma unroll
+  for (int i = 0; i < RN; i++) {
+#pragma unroll
+    for (int c = 0; c < RN; c++) rM[i * RN + c] = cm[(i * RN + c) * 64];
+    rdg[i] = rM[i * RN + i]; rdi[i] = 1.0f / rdg[i]; rdv[i] = 0.f; racc[i] = 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < RN; i++) {  // rows: setup_link_rows, with the launch constants of the lane's arm
+    const float* m0 = ln.mt.v + 3 * (f0 + i); const float* m1 = ln.mt.v + 3 * (f1 + i); cfp fa = ln.lf(f0 + i), fb = ln.lf(f1 + i);
+    const float kp = half ? m1[0] : m0[0], kd = half ? m1[1] : m0[1], maxf = half ? m1[2] : m0[2];
+    const float lower = half ? fb[DG_LF_LOWER] : fa[DG_LF_LOWER], upper = half ? fb[DG_LF_UPPER] : fa[DG_LF_UPPER];
+    smax[i] = maxf < 0.f ? -maxf : maxf * sc.hm;
+    rb[i] = kp * (tp[i] - q[i]) / h + kd * (tv[i] - qd[i]);
+    const bool limited = lower <= upper;
+    const float dlo = q[i] - lower, dhi = upper - q[i];
+    // acc < 0 marks an inactive limit row
+    lb[0][i] = -qd[i] + (dlo > 0.f ? -dlo / h : -dlo * lerp / h); la[0][i] = (limited && dlo < 0.25f) ? 0.f : -1.f;
+    lb[1][i] = qd[i] + (dhi > 0.f ? -dhi / h : -dhi * lerp / h); la[1][i] = (limited && dhi < 0.25f) ? 0.f : -1.f;
+  }
+  prof.stamp(PS_ROWS);
+  if (sc.HF[DG_HF_MOTOR_GUESS] > 0.f) chain_motor_guess(rM, rb, smax, racc, rdv, limit_ptol(sc), lb[0], la[0], lb[1], la[1]);  // (pinned limit impulses stay in la)
+  unsigned lim_rows = 0u;  // limit rows some lane of the wavefront has active: bit 2 i + side
+#pragma unroll
+  for (int i = 0; i < RN; i++) { if (__any(la[0][i] >= 0.f)) lim_rows |= 1u << (2 * i); if (__any(la[1][i] >= 0.f)) lim_rows |= 2u << (2 * i); }
+  bool live = exists; int iters_done = 0;
+  // one sweep over the six motor rows, then the limit rows the wavefront needs: the rows and the order of pgs_reg_halves
+  auto sweep = [&](auto with_limits) {
+    float maxabs = 0.f; const float lv = live ? 1.f : 0.f;
+#pragma unroll
+    for (int i = 0; i < RN; i++) {
+      const float want = racc[i] + (rb[i] - rdv[i]) * rdi[i];
+      const float nacc = __builtin_amdgcn_fmed3f(want, -smax[i], smax[i]);
+      const float delta = (nacc - racc[i]) * lv; racc[i] += delta;
+#pragma unroll
+      for (int c = 0; c < RN; c++) rdv[c] += rM[i * RN + c] * delta;
+      maxabs = fmaxf(maxabs, fabsf(delta * rdg[i]));
+    }
+    if constexpr (decltype(with_limits)::value) {
+#pragma unroll
+      for (int i = 0; i < RN; i++) {
+#pragma unroll
+        for (int side = 0; side < 2; side++) {
+          if (!((lim_rows >> (2 * i + side)) & 1u)) continue;
+          const float sg = side == 0 ? 1.f : -1.f; const bool act = la[side][i] >= 0.f;
+          const float nacc = fmaxf(la[side][i] + (lb[side][i] - sg * rdv[i]) * rdi[i], 0.f);
+          const float delta = act ? (nacc - la[side][i]) * lv : 0.f; la[side][i] += delta;
+          const float sd = sg * delta;
+#pragma unroll
+          for (int c = 0; c < RN; c++) rdv[c] += rM[i * RN + c] * sd;
+          maxabs = fmaxf(maxabs, fabsf(delta * rdg[i]));
+        }
+      }
+    }
+    const float m = half_swap_max(maxabs);  // the env's residual over both arms
+    live = live && !(m <= thr_abs);
+  };
+  // two copies of the loop (pgs_reg_halves has a third, for contact rows): the common one carries no limit code
+  if (lim_rows == 0u) {
+    for (int it = 0; it < sc.iters; it++) { if (live) iters_done = it + 1; sweep(std::false_type{}); if (!__any(live)) break; }
+  } else {
+    for (int it = 0; it < sc.iters; it++) { if (live) iters_done = it + 1; sweep(std::true_type{}); if (!__any(live)) break; }
+  }
+  prof.stamp(PS_PGS_LIMIT);
+  // apply the velocity change and integrate: the joint loop of integrate_body (its `maximp` is smax)
+  if (store) {
+#pragma unroll
+    for (int i = 0; i < RN; i++) {
+      st[(lo[i] + DG_LS_APPLIED) * stride] = smax[i] > 0.f ? racc[i] / h : 0.f;
+      const float qn = fminf(fmaxf(qd[i] + rdv[i], -vmax), vmax);
+      st[(lo[i] + DG_LS_QD) * stride] = qn; st[(lo[i] + DG_LS_Q) * stride] = q[i] + h * qn;
+    }
+  }
+  if (half == 0) col[split_slots(sc) * 64] = (float)iters_done;  // for the diagnostics column, read by the main wave after B3
+}
+
 // ---------------------------------------------------------------- substep
 // PAR: this wave is the MAIN wave of a two-wave workgroup; the helper wave (helper_substep below) owns body
 // sc.helper_body -- its kinematics and its register-resident dynamics run concurrently with everything here up to
-// the second barrier.  Both waves execute exactly three __syncthreads per substep.
+// the second barrier.  Every wavefront of the workgroup executes the same __syncthreads per substep: B1, B2, B3 when no
+// env of the workgroup has a contact (fused_free_halves), else B1, B2, Bq, [Bs when the sweeps are split,] B3.
 // SLICED (16 / 32 envs per wavefront, step kernel only): all 64 lanes are alive; lanes >= LANES sit out everything
 // except the dense Gauss-Seidel loop, where they take a share of each env's rows (pgs_dense_sliced).
 // FULLWAVE: every lane of the wavefront is active at the call (step kernels of the 64-lane and global-workspace
@@ -2096,6 +2224,7 @@ DGD void substep(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, flo
   const bool primary = SLICED ? (int)threadIdx.x < envs_per_wave(LANES) : true;
   constexpr int LCH = 6;  // links per chunk in the per-link loops
   int ncont = 0, wave_max_cont = 0, iters_done = 0;
+  bool fused = false;  // PAR: this substep takes fused_free_halves (no env of the workgroup has a contact)
   uint64_t limit_mask = 0ull;  // bit (b & 63): some lane of this wave has an active limit row on body b
   uint64_t limit_rows = 0ull;  // bit (2 gl + side), links 0..31: some lane has that limit row active (dense sweeps)
   const float thr = sc.HF[DG_HF_RESIDUAL_THRESHOLD]; const int rs = crow_stride(sc.crow_tail);
@@ -2133,6 +2262,10 @@ DGD void substep(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, flo
   }
   if (primary) {
   if (PAR) __syncthreads();  // B2: the helper's joint velocities (state) and M^-1 (LDS) are in place
+  // no contact in the workgroup: both arms go from here to B3 in the arm-per-half-wavefront mapping, without Bq / Bs
+  // (ncont and wave_max_cont stay 0; the main wave is left with the warm cache, the diagnostics and the jointless bodies)
+  if constexpr (PAR) { fused = substep_contact_free(ln); if (fused) fused_free_halves(ln, 0, prof); }
+  if (!fused) {
   if (!own_collide) {
     ncont = (int)ln.L(sc.cont_off);  // written by the narrow-phase wavefront(s) before B2
     if (sc.coll_split) {  // append the second wavefront's contacts (later pairs) behind the first's (the early first substep
@@ -2188,6 +2321,7 @@ DGD void substep(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, flo
   }
   prof.stamp(PS_ROWS);
   }
+  }  // !fused
   }  // primary
   if constexpr (SLICED) {
     // Lane-sliced modes: the SL lanes of an env's group (the grouping of the sweeps: lane = env * SL + slice) share the
@@ -2214,13 +2348,14 @@ DGD void substep(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, flo
   }
   // ---- projected Gauss-Seidel
   bool split_now = false;
-  if constexpr (PAR) split_now = split_decide_main(ln, wave_max_cont, limit_mask, limit_rows);
+  if constexpr (PAR) { if (!fused) split_now = split_decide_main(ln, wave_max_cont, limit_mask, limit_rows); }
   const bool all_dense = sc.dense && sc.nt >= 1 && sc.reg_body[0] < 0;
   if constexpr (SLICED) {  // wave-uniform results of the primary lanes, for every lane
     wave_max_cont = __builtin_amdgcn_readfirstlane(wave_max_cont);
     limit_rows = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(limit_rows >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)limit_rows);
   }
-  if (SLICED && all_dense) {
+  if (PAR && fused) {  // (swept and integrated above)
+  } else if (SLICED && all_dense) {
     const bool try_regs = sc.split_pgs != -1;  // (dg_world_create: DG_NO_REG_ROWS sets -1 for ablation / tests)
     if constexpr (SLICED && LANES == 1) {
       iters_done = pgs_wave_env<PROF>(lq, __builtin_amdgcn_readfirstlane(ncont), limit_rows, prof);
@@ -2404,17 +2539,22 @@ DGD void substep(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, flo
   }  // !all_dense
   }  // unsliced
   prof.stamp(PS_PGS);
-  if (primary) {
-  store_warm_cache(ln, ncont, wave_max_cont);
-  if (diag_out && ln.valid) {  // include/diygym_hip.h: dg_world_set_diag_buffer
+  auto write_diag = [&] {  // include/diygym_hip.h: dg_world_set_diag_buffer
     int32_t* d = diag_out + (size_t)DG_DIAG_STRIDE * ln.env;
     d[DG_DIAG_CONTACTS] = ncont; d[DG_DIAG_PGS_ITERS] = iters_done;
     if (index == 0) { d[DG_DIAG_PGS_ITERS_FIRST] = iters_done; d[DG_DIAG_CONTACTS_FIRST] = ncont; }
-  }
+  };
+  if (primary) {
+  store_warm_cache(ln, ncont, wave_max_cont);
+  if (diag_out && ln.valid && !fused) write_diag();
   // ---- apply velocity changes and integrate positions
-  for (int b = 0; b < sc.nba; b++) if (!(split_now && b == hb)) integrate_body(ln, b);  // split sweeps: the helper integrates its own body
+  // (split sweeps: the helper integrates its own body; fused substep: both arms are integrated already)
+  for (int b = 0; b < sc.nba; b++) if (!((split_now || fused) && b == hb) && !(fused && b == sc.reg_body[0])) integrate_body(ln, b);
   }  // primary
   if (PAR) __syncthreads();  // B3: positions integrated; the helper may start the next substep
+  if constexpr (PAR) {  // fused substep: the sweep counts of envs 32..63 come from the helper wave, hence after B3
+    if (fused && diag_out && ln.valid) { iters_done = (int)ln.L(split_slots(sc)); write_diag(); }
+  }
 }
 
 // the helper wave's side of one substep
@@ -2429,6 +2569,7 @@ DGD void helper_substep(const Lane<LANES>& ln, bool early, bool last) {
     const int dvo = ln.plb(hb)[PLB_DV], nv = ln.plb(hb)[PLB_NV]; for (int k = 0; k < nv; k++) ln.L(dvo + k) = 0.f;
   }
   __syncthreads();  // B2
+  if (substep_contact_free(ln)) { fused_free_halves(ln, 1, none); __syncthreads(); /* B3 */ return; }
   uint64_t lm = 0ull, lr = 0ull;
   if (sc.split_pgs) { const int hf = ln.bi(hb)[DG_BI_FIRST_LINK]; setup_link_rows(ln, hf, hf + ln.bi(hb)[DG_BI_N_LINKS], lm, lr); }
   const int hf0 = ln.bi(hb)[DG_BI_FIRST_LINK];

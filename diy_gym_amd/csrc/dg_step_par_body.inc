@@ -29,7 +29,8 @@
       __syncthreads();  // B1
       if (sc.coll_split && !(sc.early_dyn && k == 0)) collide<64, 64>(ln, sc.npairs / 2, 0x7fffffff, sc.cont2_off);  // (k == 0 with early_dyn: done above)
       __syncthreads();  // B2
-      if (split_decide_follow(ln, 0u, false)) __syncthreads();  // Bs: the sweeps run on the first two wavefronts
+      // (a substep without a contact in the workgroup has neither Bq nor Bs: the first two wavefronts run fused_free_halves)
+      if (!substep_contact_free(ln) && split_decide_follow(ln, 0u, false)) __syncthreads();  // Bs: the sweeps run on the first two wavefronts
       __syncthreads();  // B3
     }
     DG_WAVE_STAMP(2); __syncthreads();  // B4: every final pose is in LDS, every state row written
@@ -51,7 +52,7 @@
       __syncthreads();  // B1: every pose is in LDS
       if (sc.coll_wave && !(sc.early_dyn && k == 0)) collide<64, 64>(ln, 0, sc.coll_split ? sc.npairs / 2 : 0x7fffffff);  // contact list + count go to LDS; the main wave reads them after B2
       __syncthreads();  // B2
-      if (split_decide_follow(ln, false, false)) __syncthreads();  // Bs
+      if (!substep_contact_free(ln) && split_decide_follow(ln, false, false)) __syncthreads();  // Bs
       __syncthreads();  // B3
     }
     DG_WAVE_STAMP(2); __syncthreads();  // B4
