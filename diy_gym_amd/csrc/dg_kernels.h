@@ -201,11 +201,14 @@ struct Lane {
   // trip per link, and the whole call was ~10 k cycles for ~130 instructions of arithmetic per link (three calls per step: 14 %
   // of step_kernel_par).  The carried rotation is what LR() would read back -- the two stored columns and their cross product
   // -- so the poses are the same bits as the general loop's.
-  DGD void kinematics_chain(int b) const {
+  // base_rot = false leaves the base rotation's slots (PLB_R0) to another wavefront (base_rot_to_lds: the opening pose hand-over
+  // of step_kernel_par); the link poses do not depend on who stores it.
+  DGD void base_rot_to_lds(int b) const { if (!frozen(b)) LRset(plb(b)[PLB_R0], qmat(base_quat(b))); }
+  DGD void kinematics_chain(int b, bool base_rot = true) const {
     constexpr int N = 6;
     cip B = bi(b); const int first = B[DG_BI_FIRST_LINK], n = B[DG_BI_N_LINKS];
     M3 R = qmat(base_quat(b)); V3 p = base_pos(b);
-    LRset(plb(b)[PLB_R0], R);
+    if (base_rot) LRset(plb(b)[PLB_R0], R);
     float qv[N];
 #pragma unroll
     for (int j = 0; j < N; j++) qv[j] = S(li(first + min(j, n - 1))[DG_LI_STATE_OFF] + DG_LS_Q);  // every load before the first transform
@@ -221,13 +224,13 @@ struct Lane {
       }
     }
   }
-  DGD void kinematics(int b, int qoff = -1) const {
+  DGD void kinematics(int b, int qoff = -1, bool base_rot = true) const {
     cip B = bi(b);
     if (B[DG_BI_FLAGS] & DG_BODY_FROZEN) return;  // no per-env pose storage: its shapes are in world coordinates
-    if (qoff < 0 && plb(b)[PLB_CHAIN]) { kinematics_chain(b); return; }
+    if (qoff < 0 && plb(b)[PLB_CHAIN]) { kinematics_chain(b, base_rot); return; }
     int first = B[DG_BI_FIRST_LINK], n = B[DG_BI_N_LINKS];
     M3 R0 = qmat(base_quat(b)); V3 p0 = base_pos(b);
-    LRset(plb(b)[PLB_R0], R0);
+    if (base_rot) LRset(plb(b)[PLB_R0], R0);
     // joint angles eight links at a time, all loads issued before the first transform: a link at a time pays one
     // scalar-table round trip plus one global round trip per link (cold at the start of a step: ~1.4 k cycles each)
     constexpr int KCH = 8;

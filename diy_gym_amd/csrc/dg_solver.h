@@ -2695,8 +2695,30 @@ DGD int run_ik(const Lane<LANES>& ln, int op, const float* act, bool live_lane) 
 // whole solve is straight-line code (no selects, no branches, no copies at control-flow joins): ~1 000 instructions
 // per iteration instead of ~1 600.  NS / ORN: null-space projection / orientation target, fixed per instantiation.
 #define DG_IK_DEV_FULL 512
-template <int LANES, int N, bool FULL = false, bool NS = false, bool ORN = false>
-DGD int run_ik_chain(const Lane<LANES>& ln, int op, const float* act, bool live_lane, float* qout) {
+// ---- the opening pose hand-over (B0 of step_kernel_par, dg_step_par_body.inc) -----------------------------------------------
+// The register-resident solves below never read a link pose from LDS, so a wavefront that runs one need not wait for the opening
+// pose pass before it starts: it is handed a callable -- the workgroup barrier B0 and what goes with it -- which it executes between
+// its set-up (chain and null-space constants, joint angles: ~11 k cycles with the caches cold, as they are at the start of a step)
+// and its first forward kinematics, by which time the wavefronts that compute the poses meanwhile (~7.5 k) are done.  That place is
+// straight-line code, before the iteration loop and its data-dependent exits.  (At the top of iteration 1 the solve was at 19 k
+// cycles and the pose wavefronts had waited 10 k: measured)  s_barrier counts wavefronts, so the callable must run
+// EXACTLY ONCE per wavefront on every path.  Handover::operator() is idempotent, and every level calls it again behind the place
+// where the level below may have called it:
+//   run_ik_chain / run_ik_chain_pk   once, unconditionally, before the first fk()
+//   run_update_ops                   passes it to the register-chain solves only (a second such op of the wavefront finds it done)
+//   the kernel body                  again behind run_update_ops, and alone when there are no actions (no register-chain op ran:
+//                                    masked out by `mask`, a body under joint control, actions == nullptr, reset's hot-start step)
+// `done` changes only under wave-uniform control flow (scene constants, `mask`), so the barrier inside is never reached by a part
+// of a wavefront.  NoHandover is the callable of every caller that has no such barrier (all other kernels).
+struct NoHandover { DGD void operator()() const {} };
+template <class F>
+struct Handover {
+  F f; bool done;  // done = true from the start: the caller has already passed the barrier (the scene does not take the new order)
+  DGD Handover(F fn, bool d) : f(fn), done(d) {}
+  DGD void operator()() { if (!done) { done = true; f(); } }
+};
+template <int LANES, int N, bool FULL = false, bool NS = false, bool ORN = false, class HO = NoHandover>
+DGD int run_ik_chain(const Lane<LANES>& ln, int op, const float* act, bool live_lane, float* qout, HO&& ho = HO()) {
   const DevScene& sc = ln.sc; cip oi = sc.OI + op * DG_OI_STRIDE;
   const int b = oi[DG_OI_BODY], fr = oi[DG_OI_FRAME], flags = oi[DG_OI_FLAGS];
   const bool use_orn = FULL ? ORN : (flags & DG_IK_USE_ORIENTATION) != 0, nullsp = FULL ? NS : (flags & DG_IK_NULLSPACE) != 0;
@@ -2766,6 +2788,7 @@ DGD int run_ik_chain(const Lane<LANES>& ln, int op, const float* act, bool live_
     }
     pe = pl + mul(Rl, offp); Re = Rl;
   };
+  ho();  // the opening pose hand-over (above): the chain constants are loaded, the solve itself begins
   fk();
   const V3 tp = pe + v3(act[0], act[1], act[2]);
   // Orientation target as a matrix, with the frame offset folded in: the error rotation is
@@ -2879,8 +2902,8 @@ DGD P3 colmul_acc(const P3& c0, const P3& c1, const P3& c2, float x, float y, fl
 DGD P3 colmul(const P3& c0, const P3& c1, const P3& c2, float x, float y, float z) {
   P3 r; r.xy = fma2(c2.xy, sp2(z), fma2(c1.xy, sp2(y), c0.xy * sp2(x))); r.z = fmaf(c2.z, z, fmaf(c1.z, y, c0.z * x)); return r;
 }
-template <int LANES, bool ORN>
-DGD int run_ik_chain_pk(const Lane<LANES>& ln, int op, const float* act, bool live_lane, float* qout) {
+template <int LANES, bool ORN, class HO = NoHandover>
+DGD int run_ik_chain_pk(const Lane<LANES>& ln, int op, const float* act, bool live_lane, float* qout, HO&& ho = HO()) {
   constexpr int N = 6;
   const DevScene& sc = ln.sc; cip oi = sc.OI + op * DG_OI_STRIDE;
   const int b = oi[DG_OI_BODY], fr = oi[DG_OI_FRAME];
@@ -2928,6 +2951,7 @@ DGD int run_ik_chain_pk(const Lane<LANES>& ln, int op, const float* act, bool li
     }
     pe = colmul_acc(c0, c1, c2, offp.x, offp.y, offp.z, p); e0 = c0; e1 = c1; e2 = c2;
   };
+  ho();  // the opening pose hand-over (above): the chain constants are loaded, the solve itself begins
   fk();
   const V3 pe0 = v3(pe.xy.x, pe.xy.y, pe.z);
   const V3 tp = pe0 + v3(act[0], act[1], act[2]);
@@ -3082,8 +3106,11 @@ DGD void apply_frame_wrench(const Lane<LANES>& ln, int b, int fr, V3 f, V3 pos, 
 }
 
 // ------------------------------------------------------------ addon program
-template <int LANES>
-DGD void run_update_ops(const Lane<LANES>& ln, const float* act_row, uint64_t mask, int only_body = -1, int skip_body = -1, int32_t* diag = nullptr) {
+// ho: the opening pose hand-over (above), executed inside the first register-chain inverse-kinematics op that runs, if one does --
+// the caller calls it again behind this function.  No other op may need it: under the hand-over's condition (sc.early_dyn) the
+// scene has no op that reads a link pose.
+template <int LANES, class HO = NoHandover>
+DGD void run_update_ops(const Lane<LANES>& ln, const float* act_row, uint64_t mask, int only_body = -1, int skip_body = -1, int32_t* diag = nullptr, HO&& ho = HO()) {
   const DevScene& sc = ln.sc; int ik_ord = -1;
   for (int op = 0; op < sc.nops; op++) {
     cip oi = sc.OI + op * DG_OI_STRIDE; cfp of = sc.OF + op * DG_OF_STRIDE; const int code = oi[DG_OI_CODE];
@@ -3109,9 +3136,9 @@ DGD void run_update_ops(const Lane<LANES>& ln, const float* act_row, uint64_t ma
         const int fl = oi[DG_OI_FLAGS];
         // (six revolute joints, null-space lists: the packed solve; DG_NO_FULL_IK at world creation keeps such an arm on the general
         // register-resident form below -- the alternative the tests compare it with)
-        if ((fl & DG_IK_DEV_FULL) && (fl & DG_IK_NULLSPACE) && (fl & DG_IK_USE_ORIENTATION)) ik_it = run_ik_chain_pk<LANES, true>(ln, op, av, ln.valid, qs);
-        else if ((fl & DG_IK_DEV_FULL) && (fl & DG_IK_NULLSPACE)) ik_it = run_ik_chain_pk<LANES, false>(ln, op, av, ln.valid, qs);
-        else ik_it = run_ik_chain<LANES, 6>(ln, op, av, ln.valid, qs);
+        if ((fl & DG_IK_DEV_FULL) && (fl & DG_IK_NULLSPACE) && (fl & DG_IK_USE_ORIENTATION)) ik_it = run_ik_chain_pk<LANES, true>(ln, op, av, ln.valid, qs, ho);
+        else if ((fl & DG_IK_DEV_FULL) && (fl & DG_IK_NULLSPACE)) ik_it = run_ik_chain_pk<LANES, false>(ln, op, av, ln.valid, qs, ho);
+        else ik_it = run_ik_chain<LANES, 6>(ln, op, av, ln.valid, qs, ho);
         if (diag && ln.valid && ik_ord < DG_DIAG_N_IK) diag[(size_t)DG_DIAG_STRIDE * ln.env + DG_DIAG_IK_ITERS + ik_ord] = ik_it;
         const int first = ln.bi(b)[DG_BI_FIRST_LINK];
         for (int k = 0; k < n; k++) {

@@ -16,9 +16,37 @@
   const bool valid = reset_mode ? doit : exists;
   const float* act_row = actions ? actions + (size_t)e * sc.act_dim : nullptr;
   const unsigned long long t_start = PROF ? __builtin_amdgcn_s_memtime() : 0ull; (void)t_start;
+  // ---- The opening pose pass and B0 ----------------------------------------------------------------------------------------
+  // pose_ho (sc.early_dyn && sc.coll_split: wavefronts 2 and 3 both work during the update phase, an inverse-kinematics op exists,
+  // every moving body is a register chain, no update op reads a link pose; DG_NO_EARLY_DYNAMICS=1 / DG_NO_COLLIDE_SPLIT=1 switch it
+  // off): the two wavefronts that CONSUME the opening poses compute them -- wavefront 2 sc.reg_body[0]'s, wavefront 3
+  // sc.helper_body's, instead of idling at B0 -- and the two inverse-kinematics wavefronts start their solve at once and pass B0
+  // from inside it (Handover, dg_solver.h).  The base rotation (PLB_R0) of those two bodies is the one thing the solve reads from
+  // LDS: the wavefront that runs the solve stores it itself (base_rot_to_lds, before the solve in program order: no barrier
+  // needed), wavefronts 2 / 3 leave it alone (kinematics(.., base_rot = false)) and first read it behind B0 (dynamics_chain).  So
+  // between kernel start and B0 every LDS slot has one writer: PLB_R0 of both arms and every pose of any other body the main wave
+  // (the helper: its arm's PLB_R0), the link poses of the two arms wavefronts 2 / 3.
+  // Barriers each wavefront executes, in order (k = 0 .. substeps-1; Bs only in a substep with a contact that splits its sweeps):
+  //     [Br]  B0  B0'  { B1  B2  [Bs]  B3 } x substeps  B4
+  // Wavefronts 2 / 3 execute B0 in this file on every path.  Wavefronts 0 / 1 execute it through `b0`, once, here:
+  //   step with actions, packed IK (ur_high_5)    inside run_ik_chain_pk, between its set-up and its first forward kinematics
+  //   DG_NO_FULL_IK=1                             the same place in run_ik_chain<6>
+  //   a wavefront with no valid lane              the same place: it precedes the iteration loop, whose exits (no live lane at
+  //                                               it == 0, every lane converged, sc.ik_iters) therefore do not matter
+  //   the op's slot masked out by `mask`          behind run_update_ops below (no register-chain solve ran on this wavefront)
+  //   actions == nullptr                          the same call below; run_update_ops is not entered
+  //   a body under joint_controller               in a pose_ho scene: as for a masked-out op.  ur_high_5_joint has no IK op at all:
+  //                                               early_dyn == 0, pose_ho == 0, the plain order (own pose pass, then B0, in this file)
+  //   reset_kernel_par                            no env of the workgroup named: every wavefront returns before any barrier (above).
+  //                                               Otherwise Br first (all four), then the hot-start step, which has no actions:
+  //                                               the call below
+  //   !pose_ho (any other scene or switch)        the plain order: the wavefront's own pose pass, then `b0` at once
+  // `b0` is idempotent, so "again behind" never adds a barrier; see Handover for why its flag is wave-uniform.
+  const bool pose_ho = sc.early_dyn && sc.coll_split;
   if (wave == 3) {  // ---------------- second half of the narrow phase; in the early first substep, the dynamics of every second moving body
     Lane<64> ln(sc, mt, smem + lane, state + e, e, valid);
     if (reset_mode) __syncthreads();  // Br: the reset ops have written the state
+    if (pose_ho) ln.kinematics(sc.helper_body, -1, false);  // the opening poses of the helper's arm (PLB_R0: the helper)
     DG_WAVE_STAMP(0); __syncthreads();  // B0
     if (sc.early_dyn) {  // (round 4: and the second half of the early narrow phase -- the third wavefront alone was 100 k cycles against the update ops' 91 k)
       early_dynamics(ln, 1);
@@ -42,6 +70,7 @@
   if (wave == 2) {  // ---------------- narrow phase, concurrently with the two arms' dynamics (between B1 and B2)
     Lane<64> ln(sc, mt, smem + lane, state + e, e, valid);
     if (reset_mode) __syncthreads();  // Br
+    if (pose_ho) ln.kinematics(sc.reg_body[0], -1, false);  // the opening poses of the main wave's arm (PLB_R0: the main wave)
     DG_WAVE_STAMP(0); __syncthreads();  // B0
     if (sc.early_dyn) {  // first substep: narrow phase and the arms' dynamics while the first two waves run the update ops
       collide<64, 64>(ln, 0, sc.coll_split ? sc.npairs / 2 : 0x7fffffff);  // (the fourth wavefront takes every second moving body's dynamics and the other half of the pair table)
@@ -63,9 +92,10 @@
   if (wave == 1) {  // ---------------- helper
     Lane<64> ln(sc, mt, smem + lane, state + e, e, valid);
     if (reset_mode) __syncthreads();  // Br
-    ln.kinematics(sc.helper_body);
-    DG_WAVE_STAMP(0); __syncthreads();  // B0: every pose is in LDS
-    if (act_row) run_update_ops(ln, act_row, mask, sc.helper_body, -1, diag);
+    Handover b0([&]() { DG_WAVE_STAMP(0); __syncthreads(); }, false);  // B0: every pose is in LDS
+    if (pose_ho) ln.base_rot_to_lds(sc.helper_body); else { ln.kinematics(sc.helper_body); b0(); }
+    if (act_row) run_update_ops(ln, act_row, mask, sc.helper_body, -1, diag, b0);
+    b0();  // (no register-chain inverse-kinematics op ran)
     DG_WAVE_STAMP(1); __syncthreads();  // B0'
     for (int k = 0; k < sc.substeps; k++) helper_substep(ln, sc.early_dyn && k == 0, k == sc.substeps - 1);
     ln.kinematics(sc.helper_body);  // final pose of its body for the outputs
@@ -78,10 +108,12 @@
   Lane<64> ln(sc, mt, smem + lane, state + e, e, valid);
   Prof<PROF> prof; prof.start();
   if (reset_mode) { if (doit) { ln.Sset(DG_ST_STEP, 0.0f); run_reset_ops(ln); } __syncthreads(); }  // Br
-  for (int b = 0; b < sc.nba; b++) if (b != sc.helper_body) ln.kinematics(b);
-  __syncthreads();  // B0
-  prof.stamp(PS_KIN);
-  if (act_row) run_update_ops(ln, act_row, mask, -1, sc.helper_body, diag);
+  Handover b0([&]() { __syncthreads(); }, false);  // B0
+  for (int b = 0; b < sc.nba; b++) if (b != sc.helper_body) { if (pose_ho && b == sc.reg_body[0]) ln.base_rot_to_lds(b); else ln.kinematics(b); }
+  if (!pose_ho) b0();
+  prof.stamp(PS_KIN);  // (pose_ho: B0 and whatever wait it holds count as PS_UPDATE; PS_KIN is the closing pose pass alone)
+  if (act_row) run_update_ops(ln, act_row, mask, -1, sc.helper_body, diag, b0);
+  b0();  // (no register-chain inverse-kinematics op ran)
   if (!reset_mode) ln.Sset(DG_ST_STEP, ln.S(DG_ST_STEP) + 1.0f);
   __syncthreads();  // B0': the helper's motor targets are in the state
   prof.stamp(PS_UPDATE);
