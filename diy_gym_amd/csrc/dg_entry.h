@@ -109,10 +109,12 @@ __global__ __launch_bounds__(64) void reset_kernel(DevScene sc, MotorTable mt, f
     Prof<false> prof;
     for (int k = 0; k < sc.hot_start; k++) sim_step(ln, nullptr, prof);
   }
-  // observations of the envs that were reset; a wavefront without one has nothing to refresh (its rows are current)
+  // observations of the envs that were reset, and of no other: the rows of the wavefront's other envs are current and keep their
+  // bits (this kernel's arithmetic need not round as the step's or the observe kernel's did); a wavefront without one has
+  // nothing to refresh
   if (obs && (mask == nullptr || __any(doit))) {
     for (int b = 0; b < sc.nba; b++) ln.kinematics(b);
-    run_output_ops(ln, valid ? obs + (size_t)e * sc.obs_dim : nullptr, nullptr, nullptr, nullptr, nullptr, OUT_ALL, -1,
+    run_output_ops(ln, doit ? obs + (size_t)e * sc.obs_dim : nullptr, nullptr, nullptr, nullptr, nullptr, OUT_ALL, -1,
                    doit ? (sc.hot_start > 0 ? 0 : 1) : 2);
   }
 }
