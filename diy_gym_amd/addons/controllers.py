@@ -32,7 +32,8 @@ class JointController(_Controller):
 
     Configs: ``control_mode`` (``velocity``), ``joint`` | ``joints`` (all),
     ``rest_position`` (zeros).  Gains ``positionGains=0.03``, ``velocityGains=1.0``
-    and ``forces=jointMaxForce`` are the reference's (:33, :53-58).
+    and ``forces=jointMaxForce`` are the reference's (:33, :53-58).  In torque mode the action is ADDED to the joints' torques
+    for the step, on top of ``sim.apply_joint_torque`` and of external wrenches applied to the links before it.
     """
     def __init__(self, parent, config):
         super().__init__(parent, config)

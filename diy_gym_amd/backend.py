@@ -514,21 +514,23 @@ class HipBackend:
         uid included), ``frame`` the index ``Model.get_frame_id`` returns (-1: the base).  ``LINK_FRAME`` means the link's
         INERTIAL frame, as in pybullet.  The force acts during the next ``step`` only; see ``dg_world_apply_wrench``."""
         body, frame = self.layout.resolve_frame(body, frame)   # (the uid of a merged child model is an alias into its parent's body)
-        self._check(self.lib.dg_world_apply_wrench(self.handle, _ptr(self.state), int(body), int(frame), int(flags), _ptr(self._rows3('force', force)),
-                                                   _ptr(self._rows3('pos', pos)), None, self._stream()))
+        # (the converted rows are held until the launch is queued: a temporary dropped right after _ptr() hands its block back to
+        # the allocator, and the next conversion gets the same block -- force and pos would then read the same memory)
+        f, p = self._rows3('force', force), self._rows3('pos', pos)
+        self._check(self.lib.dg_world_apply_wrench(self.handle, _ptr(self.state), int(body), int(frame), int(flags), _ptr(f), _ptr(p), None, self._stream()))
 
     def apply_external_wrench(self, body, frame, force, pos, torque, flags=2):
         """Force at ``pos`` and torque in ONE launch (what the compiled ``propellor`` op does: its base torque is
         ``r x F + T`` summed before it is added to the state, so this form reproduces that op bit for bit)."""
         body, frame = self.layout.resolve_frame(body, frame)
-        self._check(self.lib.dg_world_apply_wrench(self.handle, _ptr(self.state), int(body), int(frame), int(flags), _ptr(self._rows3('force', force)),
-                                                   _ptr(self._rows3('pos', pos)), _ptr(self._rows3('torque', torque)), self._stream()))
+        f, p, t = self._rows3('force', force), self._rows3('pos', pos), self._rows3('torque', torque)   # (held until the launch is queued)
+        self._check(self.lib.dg_world_apply_wrench(self.handle, _ptr(self.state), int(body), int(frame), int(flags), _ptr(f), _ptr(p), _ptr(t), self._stream()))
 
     def apply_external_torque(self, body, frame, torque, flags=2):
         """``p.applyExternalTorque(uid, linkIndex, torqueObj, flags)`` for every env at once."""
         body, frame = self.layout.resolve_frame(body, frame)
-        self._check(self.lib.dg_world_apply_wrench(self.handle, _ptr(self.state), int(body), int(frame), int(flags), None, None,
-                                                   _ptr(self._rows3('torque', torque)), self._stream()))
+        t = self._rows3('torque', torque)
+        self._check(self.lib.dg_world_apply_wrench(self.handle, _ptr(self.state), int(body), int(frame), int(flags), None, None, _ptr(t), self._stream()))
 
     def camera_resolution(self, camera):
         I, K = self.layout.I, _scene_constants()

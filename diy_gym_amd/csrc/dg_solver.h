@@ -3125,7 +3125,9 @@ DGD void run_update_ops(const Lane<LANES>& ln, const float* act_row, uint64_t ma
         const int lo = ln.li(il[k])[DG_LI_STATE_OFF];
         if (mode == DG_JC_POSITION) { ln.Sset(lo + DG_LS_TARGET_POS, a[k]); ln.Sset(lo + DG_LS_TARGET_VEL, 0.f); }
         else if (mode == DG_JC_VELOCITY) { ln.Sset(lo + DG_LS_TARGET_VEL, a[k]); ln.Sset(lo + DG_LS_TARGET_POS, 0.f); }
-        else ln.Sset(lo + DG_LS_TORQUE, a[k]);
+        // torque mode ADDS, like the admittance and wrench ops and dg_world_apply_joint_torque: what a Python addon or an
+        // external wrench on the link put into the cell before the step stays (the cell is zeroed at the end of every step)
+        else ln.Sset(lo + DG_LS_TORQUE, ln.S(lo + DG_LS_TORQUE) + a[k]);
       }
     } else if (code == DG_OP_IK_CONTROL) {
       const int b = oi[DG_OI_BODY];

@@ -324,7 +324,7 @@ enum {
 };
 enum { DG_OF_STRIDE = 16 };
 
-/* DG_OP_JOINT_CONTROL flags */
+/* DG_OP_JOINT_CONTROL flags (torque mode ADDS the action to DG_LS_TORQUE, on top of what was applied before the step) */
 enum { DG_JC_POSITION = 0, DG_JC_VELOCITY = 1, DG_JC_TORQUE = 2 };
 /* DG_OP_IK_CONTROL flags */
 #define DG_IK_USE_ORIENTATION 1

@@ -1423,7 +1423,7 @@ static void run_update_ops(dgo_world* w, int env, const real* act, uint64_t mask
         int gl = il[k]; real* ls = st + link_i(s, gl)[DG_LI_STATE_OFF]; real maxf = link_f(s, gl)[DG_LF_MAX_FORCE];
         if (mode == DG_JC_POSITION) { ls[DG_LS_TARGET_POS] = a[k]; ls[DG_LS_TARGET_VEL] = 0.0; set_motor(w, gl, of[0], of[1], maxf); }
         else if (mode == DG_JC_VELOCITY) { ls[DG_LS_TARGET_VEL] = a[k]; ls[DG_LS_TARGET_POS] = 0.0; set_motor(w, gl, 0.0, of[1], maxf); }
-        else ls[DG_LS_TORQUE] = a[k]; /* TORQUE_CONTROL: the velocity motor is left as it was */
+        else ls[DG_LS_TORQUE] += a[k]; /* TORQUE_CONTROL: added to what is already applied for this step; the velocity motor is left as it was */
       }
     } else if (code == DG_OP_IK_CONTROL) { /* ik_controller.py:51-80 */
       real q[MAXL]; run_ik(w, st, op, a, q);
@@ -1509,6 +1509,13 @@ int dgo_apply_wrench(dgo_world* w, int32_t body, int32_t frame, int32_t link_fra
       free(ws);
     }
   }
+  return 0;
+}
+/* diagnostic: the update phase of dgo_step on its own -- run_update_ops for every env, no simulation step, no outputs: the state
+ * keeps the targets, joint torques, external wrenches and addon state the ops wrote (tests/test_input_ops_ref.py reads them) */
+int dgo_update(dgo_world* w, const real* actions, uint64_t update_mask) {
+  if (!actions) return 0;
+  for (int e = 0; e < w->B; e++) run_update_ops(w, e, actions + (size_t)e * w->sc.act_dim, update_mask);
   return 0;
 }
 static void set_base_com_pose(const Scene* s, real* st, int b, v3 pc, qt qc) {

@@ -51,6 +51,9 @@ int dgo_reset(dgo_world* w, const uint8_t* mask, real* obs);
 int dgo_step(dgo_world* w, const real* actions, uint64_t update_mask, real* obs, real* rew, uint8_t* term,
              real* rew_sum, uint8_t* term_flag);
 
+/* diagnostic: the update ops of dgo_step alone (no simulation step, no outputs); what they wrote stays in the state */
+int dgo_update(dgo_world* w, const real* actions, uint64_t update_mask);
+
 /* outputs for the current state without stepping */
 int dgo_observe(dgo_world* w, real* obs, real* rew, uint8_t* term, real* rew_sum, uint8_t* term_flag);
 

@@ -38,6 +38,7 @@ def lib(path=None):
         L.dgo_reset.argtypes = [vp, vp, vp]
         L.dgo_step.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp]
         L.dgo_observe.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.dgo_update.argtypes = [vp, vp, u64]
         L.dgo_frame_state.argtypes = [vp, i32, i32, i32, i32, vp]
         L.dgo_last_contact_count.restype = i32
         L.dgo_last_contact_count.argtypes = [vp, i32]
@@ -114,6 +115,13 @@ class OracleBackend:
         self.L.dgo_step(self.handle, _p(act) if self.act_dim else None, update_mask, _p(self.obs64), _p(self.rew64), _p(self.term8),
                         _p(self.rsum64), _p(self.tflag8))
         self._publish()
+
+    def update(self, update_mask, actions=None):
+        """The update ops of ``step`` alone (diagnostic): no simulation step, no outputs; read what they wrote with ``get_state``."""
+        if actions is None or not self.act_dim:
+            return
+        act = np.ascontiguousarray(actions.detach().cpu().numpy().astype(self.real))
+        self.L.dgo_update(self.handle, _p(act), update_mask)
 
     def observe(self):
         self.L.dgo_observe(self.handle, _p(self.obs64), _p(self.rew64), _p(self.term8), _p(self.rsum64), _p(self.tflag8))
