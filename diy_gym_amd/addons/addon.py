@@ -27,12 +27,12 @@ class AddonFactory:
 
     class _Registry:
         def __init__(self):
-            from .controllers import AdmittanceController, InverseKinematicsController, JointController, ExternalForce
+            from .controllers import AdmittanceController, InverseKinematicsController, JointController, ExternalForce, OperationalSpaceController
             from .sensors import Camera, ContactForceSensor, ContactSensor, ForceTorqueSensor, ImuSensor, JointStateSensor, JointWrenchSensor, Lidar, LinkStateSensor, ObjectStateSensor, ProximitySensor
             from .rewards import ReachTarget, ElectricityCost, TimePenalty
             from .misc import DynamicsRandomizer, Respawn, SpawnMultiple, VisualRandomizer
             from .unsupported import StuckJointCost, DrawCoords
-            # the 17 keys of reference addon.py:36-54, and `lidar`, `contact_sensor`, `contact_force_sensor`, `proximity_sensor`, `link_state_sensor`, `joint_wrench_sensor` and `imu_sensor` (no counterpart there)
+            # the 17 keys of reference addon.py:36-54, and `lidar`, `contact_sensor`, `contact_force_sensor`, `proximity_sensor`, `link_state_sensor`, `joint_wrench_sensor`, `imu_sensor` and `osc_controller` (no counterpart there)
             self.addons = {
                 'ik_controller': InverseKinematicsController,
                 'joint_controller': JointController,
@@ -58,6 +58,7 @@ class AddonFactory:
                 'link_state_sensor': LinkStateSensor,
                 'joint_wrench_sensor': JointWrenchSensor,
                 'imu_sensor': ImuSensor,
+                'osc_controller': OperationalSpaceController,
             }
 
     @staticmethod

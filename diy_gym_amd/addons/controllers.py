@@ -7,6 +7,7 @@ its pybullet calls.
 from collections import OrderedDict
 
 import numpy as np
+import torch
 
 from .. import spaces
 from ..scene import K
@@ -112,6 +113,145 @@ class InverseKinematicsController(_Controller):
                                  ilist=dofs, flist=rest + lower + upper + rng,
                                  fparams=[self.position_gain, self.velocity_gain],
                                  io_dim=6 if self.use_orientation else 3)
+
+
+def _quat_mul(a, b):
+    """Hamilton product of ``[B, 4]`` xyzw quaternions."""
+    ax, ay, az, aw = a.unbind(1)
+    bx, by, bz, bw = b.unbind(1)
+    return torch.stack((aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                        aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz), dim=1)
+
+
+def _quat_from_euler(rpy):
+    """``p.getQuaternionFromEuler`` for ``[B, 3]`` roll, pitch, yaw: xyzw."""
+    cr, cp, cy = torch.cos(0.5 * rpy).unbind(1)
+    sr, sp, sy = torch.sin(0.5 * rpy).unbind(1)
+    return torch.stack((sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy), dim=1)
+
+
+def _rotation_vector(target, current):
+    """The rotation vector, in world axes and the shortest way round, that turns ``current`` into ``target`` (``[B, 4]`` xyzw)."""
+    d = _quat_mul(target, current * current.new_tensor([-1.0, -1.0, -1.0, 1.0]))
+    d = torch.where(d[:, 3:4] < 0, -d, d)
+    s = d[:, :3].norm(dim=1, keepdim=True)
+    return d[:, :3] * torch.where(s > 1e-8, 2.0 * torch.atan2(s, d[:, 3:4]) / s.clamp_min(1e-8), torch.full_like(s, 2.0))
+
+
+class OperationalSpaceController(Addon):
+    """Operational-space (Cartesian impedance) control of an end effector with joint torques -- robosuite's ``OSC_POSE`` -- written
+    ONLY on the ``env.sim`` query contract the README gives user addons: a hook addon, no ``compile()`` op, no counterpart in the
+    reference.  The torque is ``J^T Lambda (acc - Jdot qd) + h`` (+ a posture torque through the dynamically consistent null-space
+    projector), with ``acc = [kp (p* - p) - kd v; kp_r e_R - kd_r w]`` towards a PERSISTENT per-env target pose ``(p*, q*)`` that the
+    actions move: ``p* += linear``, ``q* <- q* (x) euler(rotation)``.  (The reference's ``ik_controller``, whose action spaces these
+    are, re-reads the CURRENT pose every tick and adds the action to that instead; a target that persists does not drift with the
+    tracking error.)
+
+    Configs: ``end_effector`` (required), ``offset`` ([0, 0, 0], in the end-effector link's inertial frame), ``use_orientation``
+    (yes; no: the three translational rows only), ``rest_position`` (zeros), ``stiffness`` ([100, 100]: translational and
+    rotational ``kp``), ``damping_ratio`` (1.0: ``kd = 2 ratio sqrt(kp)``), ``posture_stiffness`` (0.0; when > 0 and the task has
+    fewer rows than the body joints, ``tau0 = k (rest - q) - 2 sqrt(k) qd``), ``lambda_damping`` (0.0, added to the diagonal of
+    ``J M^-1 J^T``), ``clip_torque`` (yes: the torque is clamped to the joints' URDF effort limits -- ``joint_controller``'s ``torque_limit``;
+    the default motor row that reset() switches off holds an impulse bound, not the effort).
+
+    Per tick: one ``task_space_dynamics`` for the point's pose and velocity, torch arithmetic for ``acc``, one
+    ``task_space_dynamics`` for the torque, one ``apply_joint_torque`` (with a posture term, a ``joint_states`` before them).
+    ``reset()`` switches the body's default velocity motors off once, puts the joints of the envs in ``env.reset_mask`` at
+    ``rest_position`` and their target at the task point's pose there.  ``set_target(pos, orn, mask)`` moves the target by hand."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        if not hasattr(parent, 'robot'):
+            raise ValueError('osc_controller goes on a model, not on the environment')
+        if 'end_effector' not in config:
+            raise ValueError('osc_controller: end_effector is required')
+        self.uid = parent.uid
+        robot = parent.robot
+        self.end_frame = parent.get_frame_id(config.get('end_effector'))
+        if self.end_frame < 0:
+            raise ValueError('osc_controller: unknown end_effector %r' % (config.get('end_effector'), ))
+        self.nv = robot.num_dofs
+        self.offset = [float(v) for v in config.get('offset', [0., 0., 0.])]
+        self.use_orientation = bool(config.get('use_orientation', True))
+        self.axes = (0, 1, 2, 3, 4, 5) if self.use_orientation else (0, 1, 2)
+        self.rest_position = [float(v) for v in config.get('rest_position', [0.] * self.nv)]
+        stiffness = [float(v) for v in config.get('stiffness', [100., 100.])]
+        self.damping_ratio = float(config.get('damping_ratio', 1.0))
+        self.posture_stiffness = float(config.get('posture_stiffness', 0.0))
+        self.lambda_damping = float(config.get('lambda_damping', 0.0))
+        self.clip_torque = bool(config.get('clip_torque', True))
+        if len(self.offset) != 3:
+            raise ValueError('osc_controller: offset must have 3 elements, got %d' % len(self.offset))
+        if len(self.rest_position) != self.nv:
+            raise ValueError('osc_controller: rest_position has %d entries, the body has %d joints' % (len(self.rest_position), self.nv))
+        if len(stiffness) != 2 or min(stiffness) < 0:
+            raise ValueError('osc_controller: stiffness must be [translational, rotational] >= 0, got %r' % (stiffness, ))
+        if len(self.axes) > self.nv:
+            raise ValueError('osc_controller: %d task rows for a body of %d joints' % (len(self.axes), self.nv))
+        if min(self.damping_ratio, self.posture_stiffness, self.lambda_damping) < 0:
+            raise ValueError('osc_controller: damping_ratio, posture_stiffness and lambda_damping must be >= 0')
+        self.stiffness = stiffness
+        self.posture = self.posture_stiffness > 0 and len(self.axes) < self.nv
+        self.torque_limit = [float(j.effort) for j in robot.joints if j.q_index > -1]   # in q_index order (the URDF's depth-first joints)
+        sp = OrderedDict(linear=spaces.Box(-0.01, 0.01, shape=(3, ), dtype='float32'))
+        if self.use_orientation:
+            sp['rotation'] = spaces.Box(-0.01, 0.01, shape=(3, ), dtype='float32')
+        self.action_space = spaces.Dict(sp)
+        self._ready = False
+
+    def _point(self, q=None):
+        return self.env.sim.task_space_dynamics(self.uid, self.end_frame, self.offset, self.axes, q=q, want=('point', )).point
+
+    def reset(self):
+        env = self.env
+        sim, L = env.sim, env.layout
+        if not self._ready:
+            first = L.body_first_link[L.resolve_frame(self.uid, -1)[0]]
+            rows = [first + i for i in range(self.nv)]
+            cfg = sim.motor_cfg()
+            self._effort = torch.tensor(self.torque_limit, dtype=torch.float32, device=sim.device)
+            cfg[rows, 2] = 0.0   # the default velocity motors off: p.setJointMotorControlArray(..., VELOCITY_CONTROL, forces=[0] * n)
+            sim.set_motor_cfg(cfg)
+            kp = [self.stiffness[0]] * 3 + ([self.stiffness[1]] * 3 if self.use_orientation else [])
+            self._kp = torch.tensor(kp, dtype=torch.float32, device=sim.device)
+            self._kd = 2.0 * self.damping_ratio * torch.sqrt(self._kp)
+            self._rest = torch.tensor(self.rest_position, dtype=torch.float32, device=sim.device)
+            self.target_pos = torch.zeros((sim.num_envs, 3), dtype=torch.float32, device=sim.device)
+            self.target_orn = torch.zeros((sim.num_envs, 4), dtype=torch.float32, device=sim.device)
+            self._ready = True
+        sim.reset_joint_state(self.uid, self._rest, mask=env.reset_mask)
+        self.set_target(*self._point(self._rest)[:, :7].split((3, 4), dim=1), mask=env.reset_mask)
+
+    def set_target(self, pos, orn=None, mask=None):
+        """The target pose of the envs ``mask`` selects (None: all): ``pos`` ``[B, 3]`` or ``[3]``, ``orn`` a unit quaternion xyzw
+        ``[B, 4]`` or ``[4]`` (None: left as it is)."""
+        sim = self.env.sim
+        rows = None if mask is None else torch.as_tensor(mask, device=sim.device).reshape(sim.num_envs, 1) != 0
+        for name, value, width in (('target_pos', pos, 3), ('target_orn', orn, 4)):
+            if value is not None:
+                new = self.env._as_batch(value, width)
+                setattr(self, name, new.clone() if rows is None else torch.where(rows, new, getattr(self, name)))
+
+    def update(self, action):
+        env = self.env
+        sim = env.sim
+        self.target_pos = self.target_pos + env._as_batch(action['linear'], 3)
+        if self.use_orientation:
+            q = _quat_mul(self.target_orn, _quat_from_euler(env._as_batch(action['rotation'], 3)))
+            self.target_orn = q / q.norm(dim=1, keepdim=True)
+        tau_null = None
+        if self.posture:
+            joint_positions, joint_velocities = sim.joint_states(self.uid)
+            k = self.posture_stiffness
+            tau_null = k * (self._rest - joint_positions) - 2.0 * k ** 0.5 * joint_velocities
+        point = self._point()
+        err = [self.target_pos - point[:, 0:3]] + ([_rotation_vector(self.target_orn, point[:, 3:7])] if self.use_orientation else [])
+        vel = point[:, 7:13] if self.use_orientation else point[:, 7:10]
+        acc = self._kp * torch.cat(err, dim=1) - self._kd * vel
+        tau = sim.task_space_dynamics(self.uid, self.end_frame, self.offset, self.axes, acc=acc, tau_null=tau_null, damping=self.lambda_damping,
+                                      want=('tau', )).tau
+        if self.clip_torque:
+            tau = torch.where(self._effort > 0, torch.minimum(torch.maximum(tau, -self._effort), self._effort), tau)
+        sim.apply_joint_torque(self.uid, tau)
 
 
 class ExternalForce(_Controller):

@@ -70,6 +70,8 @@ SYMBOLS = {
     'dg_world_joint_wrench': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.POINTER(JointSelector), ctypes.c_int32, _vp, _vp]),
     'dg_world_joint_efforts': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp]),
     'dg_world_link_accelerations': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.POINTER(AccelSelector), ctypes.c_int32, _vp, _vp]),
+    'dg_world_task_space': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, _vp, _vp, _vp, _vp,
+                                             ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
     'dg_world_closest': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -126,6 +128,9 @@ ClosestPoints = collections.namedtuple('ClosestPoints', ['count', 'id_a', 'id_b'
 CLOSEST_MAX_POINTS = 64   # the cap of closest_points' default K
 LINK_STATES_MAX = 32   # DG_LINK_STATES_MAX: (body, frame) selectors of one link_states call
 JOINT_WRENCH_MAX = 16   # DG_JOINT_WRENCH_MAX: joint selectors of one joint_reaction_forces call
+# what task_space_dynamics returns: device tensors, None for the outputs `want` left out.  `lambda` is a Python keyword: the field
+# is `lambda_` (`want` takes either spelling)
+TaskSpaceDynamics = collections.namedtuple('TaskSpaceDynamics', ['jac', 'bias_acc', 'bias_torque', 'lambda_', 'tau', 'point', 'singular'])
 LINK_ACCEL_MAX = 16   # DG_LINK_ACCEL_MAX: sensor-frame selectors of one link_accelerations call
 # what link_accelerations returns: [B, n, 3] views of ONE [B, n, 15] buffer, at the columns DG_LA_* of include/diygym_hip.h
 LinkAccelerations = collections.namedtuple('LinkAccelerations', ['lin_acc', 'ang_acc', 'specific_force', 'ang_vel', 'gravity'])
@@ -681,6 +686,58 @@ class HipBackend:
         if torque is None:
             raise ValueError('torque must be a torch.Tensor, got None')
         self._dyn_check(self.lib.dg_world_apply_joint_torque(self.handle, _ptr(self.state), body, _ptr(self._rows_nv('torque', torque, nv)), self._stream()))
+
+    # -- task-space dynamics: what an operational-space controller needs per tick, in one launch ------------------------------
+    def task_space_dynamics(self, body, frame, local_pos=(0.0, 0.0, 0.0), axes=(0, 1, 2, 3, 4, 5), q=None, qd=None, acc=None, tau_null=None, damping=0.0,
+                            want=('jac', 'bias_acc', 'bias_torque', 'lambda', 'tau', 'point', 'singular')):
+        """The task-space dynamics of the point ``local_pos`` (INERTIAL frame of ``frame``'s link, as ``calculate_jacobian`` takes
+        it) for every env in ONE launch (``dg_world_task_space``).  The task vector is ``[v; w]`` of the point in world axes;
+        ``axes`` names the ``m`` rows kept (distinct indices 0 .. 5, taken in increasing order).  ``q`` / ``qd`` default to each
+        env's current values; ``acc`` ``[B, m]`` is the desired task acceleration, ``tau_null`` ``[B, nv]`` a joint torque applied
+        through the dynamically consistent null-space projector, ``damping`` >= 0 is added to the diagonal of ``J M^-1 J^T``.
+        Returns a ``TaskSpaceDynamics``: ``jac [B, m, nv]``, ``bias_acc [B, m]`` (``Jdot qd``), ``bias_torque [B, nv]``
+        (``C qd - G``), ``lambda_ [B, m, m]`` (``(J M^-1 J^T + damping I)^-1``, symmetric in bits; ``want`` spells it ``'lambda'``),
+        ``tau [B, nv]`` (``J^T Lambda (acc - Jdot qd) + h + N^T tau_null``), ``point [B, 13]`` (position, quaternion xyzw of the
+        link's inertial frame, linear and angular velocity) and ``singular [B]`` int32 (1: a pivot sat at the floor, see the C
+        header).  Fields not in ``want`` are None; ``tau`` leaves the default ``want`` when ``acc`` is None.  The tensors are
+        views of buffers kept per ``(m, want)`` and REUSED by the next call: clone what must last.  ValueError, before anything is
+        launched, for everything the entry refuses (a body or frame the dynamics queries do not take, no or bad ``axes``, more rows
+        than joints, a negative or non-finite ``damping``, an empty ``want``, ``'tau'`` without ``acc``, ``tau_null`` without
+        ``'tau'``) and for tensors of the wrong shape, dtype or device."""
+        if int(frame) < 0:
+            raise ValueError('frame must be a frame id >= 0, got %d' % int(frame))
+        body, frame, nv = self._dyn_body(body, frame)
+        lp = np.asarray(local_pos, dtype=np.float32).reshape(-1)
+        if lp.size != 3:
+            raise ValueError('local_pos must have 3 elements, got %d' % lp.size)
+        axes = [int(a) for a in axes]
+        if len(set(axes)) != len(axes) or any(a < 0 for a in axes):
+            raise ValueError('axes must be distinct indices 0 .. 5 of [v; w], got %r' % (axes, ))
+        # what the shapes below depend on is refused here, in the entry's words; the entry refuses the rest before it launches
+        m, mask = len(axes), sum(1 << min(a, 30) for a in axes)
+        if mask <= 0 or mask > 63:
+            raise ValueError('dg_world_task_space: axes_mask %d selects no row or a row above 5 of [v; w]' % mask)
+        if m > nv:
+            raise ValueError('dg_world_task_space: %d task rows for a body of %d joints' % (m, nv))
+        fields = TaskSpaceDynamics._fields
+        every = tuple(f.rstrip('_') for f in fields)
+        names = ['lambda_' if n == 'lambda' else n for n in want]
+        if set(names) - set(fields):
+            raise ValueError('want must name some of %r, got %r' % (every, want))
+        if acc is None and tuple(want) == every:   # (the default)
+            names.remove('tau')
+        q, qd, tau_null = self._rows_nv('q', q, nv), self._rows_nv('qd', qd, nv), self._rows_nv('tau_null', tau_null, nv)
+        acc = self._rows_nv('acc', acc, m)
+        key = ('task_space', body, m, tuple(f in names for f in fields))
+        if key not in self._dyn_out:
+            B = self.num_envs
+            shapes = {'jac': (B, m, nv), 'bias_acc': (B, m), 'bias_torque': (B, nv), 'lambda_': (B, m, m), 'tau': (B, nv), 'point': (B, 13), 'singular': (B, )}
+            self._dyn_out[key] = TaskSpaceDynamics(*[torch.zeros(shapes[f], dtype=torch.int32 if f == 'singular' else torch.float32, device=self.device)
+                                                     if f in names else None for f in fields])
+        out = self._dyn_out[key]
+        self._dyn_check(self.lib.dg_world_task_space(self.handle, _ptr(self.state), body, frame, (ctypes.c_float * 3)(*lp.tolist()), mask, _ptr(q), _ptr(qd),
+                                                     _ptr(acc), _ptr(tau_null), float(damping), *[_ptr(t) for t in out], self._stream()))
+        return out
 
     # -- the second half of p.getJointState(s): jointReactionForces, appliedJointMotorTorque ------------------------------------
     def joint_reaction_forces(self, body, joints=None):

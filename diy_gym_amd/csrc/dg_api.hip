@@ -21,6 +21,7 @@
 #include "dg_ikq.h"
 #include "dg_jointq.h"
 #include "dg_accelq.h"
+#include "dg_taskq.h"
 
 using namespace dg;
 
@@ -771,6 +772,27 @@ int32_t dg_world_link_accelerations(dg_world* w, const float* state, int32_t bod
   if (gn > 0.0) { sel.ghat[0] = (float)(w->sc.gx / gn); sel.ghat[1] = (float)(w->sc.gy / gn); sel.ghat[2] = (float)(w->sc.gz / gn); }
   // the grid and block of reset_kernel, as dg_world_joint_wrench
   return launch(w, stream, &LaunchTable::link_accel, state, body, sel, out);
+}
+
+// ------------------------------------------------------------------ task-space dynamics (dg_taskq.h)
+int32_t dg_world_task_space(dg_world* w, const float* state, int32_t body, int32_t frame, const float* local_pos, int32_t axes_mask, const float* q, const float* qd,
+                            const float* acc, const float* tau_null, float damping, float* jac, float* bias_acc, float* bias_torque, float* lambda, float* tau,
+                            float* point, int32_t* singular, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_task_space")) return rc;
+  if (!local_pos) return fail(DG_ERR_ARG, "dg_world_task_space: local_pos is NULL (three host floats)");
+  if (frame < 0) return fail(DG_ERR_ARG, "dg_world_task_space: frame %d out of range (the base of a fixed body does not move)", frame);
+  int gf;
+  if (const int rc = frame_check(w, body, frame, &gf, "dg_world_task_space")) return rc;
+  if (axes_mask <= 0 || axes_mask > 63) return fail(DG_ERR_ARG, "dg_world_task_space: axes_mask %d selects no row or a row above 5 of [v; w]", axes_mask);
+  const int n = body_row(w, body)[DG_BI_N_LINKS], m = __builtin_popcount((unsigned)axes_mask);
+  if (m > n) return fail(DG_ERR_ARG, "dg_world_task_space: %d task rows for a body of %d joints", m, n);
+  if (!(damping >= 0.f) || !std::isfinite(damping)) return fail(DG_ERR_ARG, "dg_world_task_space: damping must be finite and >= 0, got %g", (double)damping);
+  if (!jac && !bias_acc && !bias_torque && !lambda && !tau && !point && !singular) return fail(DG_ERR_ARG, "dg_world_task_space: every output is NULL");
+  if (tau && !acc) return fail(DG_ERR_ARG, "dg_world_task_space: tau needs acc");
+  if (tau_null && !tau) return fail(DG_ERR_ARG, "dg_world_task_space: tau_null without tau");
+  if (taskq_slots(n, m) > w->sc.tr_slots) return slots_refusal(w, body, taskq_slots(n, m), "dg_world_task_space");
+  return launch(w, stream, &LaunchTable::task_space, state, body, gf, local_pos[0], local_pos[1], local_pos[2], (int)axes_mask, q, qd, acc, tau_null, damping,
+                jac, bias_acc, bias_torque, lambda, tau, point, singular);
 }
 
 // ------------------------------------------------------------------ closest-points query (dg_closestq.h)

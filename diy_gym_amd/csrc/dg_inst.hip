@@ -20,6 +20,7 @@
 #include "dg_stateq.h"
 #include "dg_jointq.h"
 #include "dg_accelq.h"
+#include "dg_taskq.h"
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
 #include "dg_closestq.h"
 #endif

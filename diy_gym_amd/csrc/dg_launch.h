@@ -53,7 +53,10 @@ struct LaSelectors { int32_t n; float ghat[3]; dg_accel_selector s[DG_LINK_ACCEL
   X(joint_wrench, int body, const JwSelectors& sel, float* wrench, float* gws) \
   X(joint_effort, int body, float* out, float* gws) \
   /* link accelerations, IMU readings (dg_accelq.h) */ \
-  X(link_accel, int body, const LaSelectors& sel, float* out, float* gws)
+  X(link_accel, int body, const LaSelectors& sel, float* out, float* gws) \
+  /* task-space dynamics (dg_taskq.h) */ \
+  X(task_space, int body, int frame, float lx, float ly, float lz, int axes_mask, const float* q, const float* qd, const float* acc, const float* tau_null, \
+    float damping, float* jac, float* bias_acc, float* bias_torque, float* lambda, float* tau, float* point, int32_t* singular, float* gws)
 
 struct LaunchTable {
   bool has_prof;

@@ -499,6 +499,36 @@ typedef struct dg_accel_selector {
 int32_t dg_world_link_accelerations(dg_world* w, const float* state, int32_t body,
     const dg_accel_selector* selectors /* host [n] */, int32_t n, float* out /* [num_envs][n][15] */, void* stream);
 
+/* Task-space dynamics of one point of a fixed-base articulated body, every env at once, in ONE launch: what an operational-space
+ * (Cartesian impedance) controller needs per tick.  Same bodies and rules as the dynamics queries: device float32 arrays, nothing
+ * allocated, freed or synchronised; `frame` and local_pos[3] (HOST floats) as dg_world_jacobian takes them.  The task vector is
+ * [v; w] of that point in world axes; bit k of axes_mask (k = 0 .. 5) selects its row k, m is the number of set bits, nv the
+ * body's number of joints.
+ *   q, qd      [num_envs][nv] or NULL = the env's own values (a NULL call and a call given the same numbers are the same bits)
+ *   acc        [num_envs][m] or NULL: the desired task acceleration (required by tau)
+ *   tau_null   [num_envs][nv] or NULL: a joint torque to be applied through the dynamically consistent null-space projector
+ *   damping    >= 0, added to the diagonal of J M^-1 J^T
+ * Outputs; each may be NULL, at least one must not be:
+ *   jac          [num_envs][m][nv]  the selected rows of [jac_t; jac_r]
+ *   bias_acc     [num_envs][m]      the selected rows of Jdot qd: the task acceleration at qdd = 0
+ *   bias_torque  [num_envs][nv]     h = C qd - G: dg_world_inverse_dynamics(q, qd, 0)
+ *   lambda       [num_envs][m][m]   (J M^-1 J^T + damping I)^-1, symmetric in bits
+ *   tau          [num_envs][nv]     J^T lambda (acc - Jdot qd) + h + (tau_null - J^T lambda J M^-1 tau_null)
+ *   point        [num_envs][13]     the point's position, the quaternion (xyzw) of the link's inertial frame, the point's
+ *                                   linear velocity and the link's angular velocity at the q, qd worked at
+ *   singular     [num_envs] int32   1 when a pivot of the Cholesky factorisation of M or of J M^-1 J^T + damping I was <= 1e-5 x
+ *                                   the largest diagonal entry of the matrix factored; the pivot is then that floor, so every
+ *                                   output stays finite.  M is taken in its Jacobi-scaled form (unit diagonal: pivot j against
+ *                                   1e-5 x M[j][j]), so that a tree of very unequal links -- an arm with a gripper -- is not
+ *                                   flagged for its sizes
+ * DG_ERR_ARG (nothing launched, outputs untouched) for what the dynamics queries refuse, an axes_mask with no bit or a bit above 5,
+ * m > nv, a damping that is negative or not finite, every output NULL, tau without acc, tau_null without tau, and a body whose
+ * pass would need more workspace than the world has. */
+int32_t dg_world_task_space(dg_world* w, const float* state, int32_t body, int32_t frame, const float* local_pos, int32_t axes_mask,
+                            const float* q, const float* qd, const float* acc, const float* tau_null, float damping,
+                            float* jac, float* bias_acc, float* bias_torque, float* lambda, float* tau, float* point, int32_t* singular,
+                            void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
