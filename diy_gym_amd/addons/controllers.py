@@ -254,6 +254,139 @@ class OperationalSpaceController(Addon):
         sim.apply_joint_torque(self.uid, tau)
 
 
+class MppiController(Addon):
+    """Sampling model-predictive control (MPPI) of an end effector's position with joint torques, written ONLY on the ``env.sim``
+    query contract: a hook addon, no ``compile()`` op, no counterpart in the reference.  Every tick ``samples`` candidate torque
+    sequences per env are rolled ``horizon`` steps through the arm's own rigid-body model in ONE ``rollout_joint_dynamics`` launch
+    and the nominal sequence moves towards the cheap ones.
+
+    Configs: ``end_effector`` (required), ``offset`` ([0, 0, 0], in the end-effector link's inertial frame), ``samples`` (64),
+    ``horizon`` (16), ``dt`` (the model's step; default 4 x the scene's substep), ``noise`` (0.1: the standard deviation of the
+    torque noise as a fraction of each joint's URDF effort limit; a joint without a limit takes ``noise`` N m), ``temperature``
+    (1.0), ``weights`` (``{position: 1, terminal_velocity: 0.01, torque: 0}``), ``joint_damping`` (yes: the model applies the
+    joints' URDF damping, as the step does), ``clip_torque`` (yes: sampled and applied torques are clamped to the effort limits).
+
+    The action ``linear`` [3] is ADDED to a per-env target position that persists (``osc_controller``'s rule); ``set_target(pos,
+    mask)`` sets it directly.  Per tick: the nominal sequence ``U [B, T, nv]`` is shifted by one step (a zero enters at the end);
+    ``g = calculate_inverse_dynamics(qd=0, qdd=0)`` is the gravity compensation at the current pose; sample k is
+    ``g + U + eps_k`` with Gaussian ``eps`` (sample 0 carries none: the nominal sequence itself is always a candidate);
+    ``cost_k = w_p sum_t |pos_t - target|^2 + w_v |qd_T|^2 + w_u sum |eps_k|^2``; ``U += softmax(-c_k / temperature) . eps`` with
+    ``c_k = (cost_k - min cost) / mean(cost - min cost)`` per env -- the costs enter relative to their own spread, so that
+    ``temperature`` has no unit and 1.0 gives the average sample 1 / e of the best one's weight whatever the scene's scale; then
+    ``apply_joint_torque(g + U[:, 0])``.  That is four ``env.sim`` calls: ``calculate_inverse_dynamics``,
+    ``rollout_joint_dynamics(..., want=('qd', 'pos'))``, ``apply_joint_torque``, and before them one
+    ``task_space_dynamics(want=('point', ))`` on the first tick after a reset only, which re-reads the target from the pose the
+    reset left.  The model has no joint limits, motors, link damping or contacts: what it does not know, the next tick corrects.
+
+    ``reset()`` switches the body's default velocity motors off once and, for the envs in ``env.reset_mask``, clears the nominal
+    sequence and marks the target to be re-read.  The noise comes from a ``torch.Generator`` seeded from the env's seed when the
+    addon first resets: the same seed, process and batch give the same torques in bits; it is NOT shard-invariant (a shard draws
+    for its own batch)."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        if not hasattr(parent, 'robot'):
+            raise ValueError('mppi_controller goes on a model, not on the environment')
+        if 'end_effector' not in config:
+            raise ValueError('mppi_controller: end_effector is required')
+        self.uid = parent.uid
+        robot = parent.robot
+        self.end_frame = parent.get_frame_id(config.get('end_effector'))
+        if self.end_frame < 0:
+            raise ValueError('mppi_controller: unknown end_effector %r' % (config.get('end_effector'), ))
+        self.nv = robot.num_dofs
+        self.offset = [float(v) for v in config.get('offset', [0., 0., 0.])]
+        self.samples, self.horizon = int(config.get('samples', 64)), int(config.get('horizon', 16))
+        self.dt = None if 'dt' not in config else float(config.get('dt'))
+        self.noise, self.temperature = float(config.get('noise', 0.1)), float(config.get('temperature', 1.0))
+        weights = config.get('weights', {}) or {}
+        weights = dict(getattr(weights, 'node', weights))   # (a mapping comes back as a Configuration)
+        if set(weights) - {'position', 'terminal_velocity', 'torque'}:
+            raise ValueError('mppi_controller: weights takes position, terminal_velocity and torque, got %r' % (sorted(weights), ))
+        self.w_position, self.w_velocity, self.w_torque = (float(weights.get(k, d)) for k, d in (('position', 1.0), ('terminal_velocity', 0.01), ('torque', 0.0)))
+        self.joint_damping = bool(config.get('joint_damping', True))
+        self.clip_torque = bool(config.get('clip_torque', True))
+        if len(self.offset) != 3:
+            raise ValueError('mppi_controller: offset must have 3 elements, got %d' % len(self.offset))
+        if self.samples < 1 or self.horizon < 1:
+            raise ValueError('mppi_controller: samples and horizon must be >= 1, got %d and %d' % (self.samples, self.horizon))
+        if self.dt is not None and not self.dt > 0:
+            raise ValueError('mppi_controller: dt must be > 0, got %g' % self.dt)
+        if not self.noise > 0 or not self.temperature > 0:
+            raise ValueError('mppi_controller: noise and temperature must be > 0')
+        if min(self.w_position, self.w_velocity, self.w_torque) < 0:
+            raise ValueError('mppi_controller: weights must be >= 0')
+        self.torque_limit = [float(j.effort) for j in robot.joints if j.q_index > -1]   # in q_index order (the URDF's depth-first joints)
+        self.action_space = spaces.Dict(OrderedDict(linear=spaces.Box(-0.01, 0.01, shape=(3, ), dtype='float32')))
+        self._ready = False
+
+    def reset(self):
+        env = self.env
+        sim, L = env.sim, env.layout
+        B = sim.num_envs
+        if not self._ready:
+            first = L.body_first_link[L.resolve_frame(self.uid, -1)[0]]
+            rows = [first + i for i in range(self.nv)]
+            cfg = sim.motor_cfg()
+            cfg[rows, 2] = 0.0   # the default velocity motors off: p.setJointMotorControlArray(..., VELOCITY_CONTROL, forces=[0] * n)
+            sim.set_motor_cfg(cfg)
+            new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=sim.device)
+            self._effort = torch.tensor(self.torque_limit, dtype=torch.float32, device=sim.device)
+            self._sigma = self.noise * torch.where(self._effort > 0, self._effort, torch.ones_like(self._effort))
+            if self.dt is None:
+                self.dt = 4.0 * L.dt
+            self._gen = torch.Generator(device=sim.device)
+            self._gen.manual_seed(int(env.np_random.integers(2 ** 31)))   # (env.np_random is seeded with the env's seed and read by nothing else)
+            self.nominal = new(B, self.horizon, self.nv)
+            self.target_pos = new(B, 3)
+            self._zero = new(B, self.nv)
+            self._stale = torch.ones((B, 1), dtype=torch.bool, device=sim.device)
+            self._ready = True
+        rows = torch.ones((B, 1), dtype=torch.bool, device=sim.device) if env.reset_mask is None else torch.as_tensor(env.reset_mask, device=sim.device).reshape(B, 1) != 0
+        self.nominal = torch.where(rows[:, :, None], torch.zeros_like(self.nominal), self.nominal)
+        self._stale = self._stale | rows
+        self._any_stale = True
+
+    def set_target(self, pos, mask=None):
+        """The target position of the envs ``mask`` selects (None: all): ``pos`` ``[B, 3]`` or ``[3]``."""
+        sim = self.env.sim
+        rows = torch.ones((sim.num_envs, 1), dtype=torch.bool, device=sim.device) if mask is None else torch.as_tensor(mask, device=sim.device).reshape(sim.num_envs, 1) != 0
+        self.target_pos = torch.where(rows, self.env._as_batch(pos, 3), self.target_pos)
+        self._stale = self._stale & ~rows
+
+    def _clip(self, tau):
+        return torch.where(self._effort > 0, torch.minimum(torch.maximum(tau, -self._effort), self._effort), tau)
+
+    def update(self, action):
+        env = self.env
+        sim = env.sim
+        if self._any_stale:   # the first tick after a reset: the target is the pose that reset left
+            point = sim.task_space_dynamics(self.uid, self.end_frame, self.offset, (0, 1, 2), want=('point', )).point
+            self.target_pos = torch.where(self._stale, point[:, 0:3], self.target_pos)
+            self._stale = torch.zeros_like(self._stale)
+            self._any_stale = False
+        self.target_pos = self.target_pos + env._as_batch(action['linear'], 3)
+        B, K, T, nv = sim.num_envs, self.samples, self.horizon, self.nv
+        U = torch.cat([self.nominal[:, 1:], torch.zeros_like(self.nominal[:, :1])], dim=1)
+        g = sim.calculate_inverse_dynamics(self.uid, qd=self._zero)
+        eps = torch.randn((B, K, T, nv), generator=self._gen, dtype=torch.float32, device=sim.device) * self._sigma
+        eps[:, 0] = 0.0
+        mean = (g[:, None, :] + U)[:, None]
+        tau = mean + eps
+        if self.clip_torque:
+            tau = self._clip(tau)
+            eps = tau - mean
+        roll = sim.rollout_joint_dynamics(self.uid, tau.contiguous(), dt=self.dt, frame=self.end_frame, local_pos=self.offset, joint_damping=self.joint_damping,
+                                          want=('qd', 'pos'))
+        cost = (self.w_position * (roll.pos - self.target_pos[:, None, None, :]).square().sum(dim=(2, 3)) + self.w_velocity * roll.qd[:, :, -1].square().sum(dim=2)
+                + self.w_torque * eps.square().sum(dim=(2, 3)))
+        rel = cost - cost.min(dim=1, keepdim=True).values
+        rel = rel / rel.mean(dim=1, keepdim=True).clamp_min(1e-30)
+        weight = torch.softmax(-rel / self.temperature, dim=1)
+        self.nominal = U + (weight[:, :, None, None] * eps).sum(dim=1)
+        torque = g + self.nominal[:, 0]
+        sim.apply_joint_torque(self.uid, self._clip(torque) if self.clip_torque else torque)
+
+
 class ExternalForce(_Controller):
     """World-frame force on the base for the next step (reference:
     diy_gym/addons/controllers/external_force.py:9-24).  ``xyz`` is passed as

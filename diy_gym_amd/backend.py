@@ -72,6 +72,9 @@ SYMBOLS = {
     'dg_world_link_accelerations': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.POINTER(AccelSelector), ctypes.c_int32, _vp, _vp]),
     'dg_world_task_space': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, _vp, _vp, _vp, _vp,
                                              ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_forward_dynamics': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
+    'dg_world_rollout': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                          ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
     'dg_world_closest': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -131,6 +134,8 @@ JOINT_WRENCH_MAX = 16   # DG_JOINT_WRENCH_MAX: joint selectors of one joint_reac
 # what task_space_dynamics returns: device tensors, None for the outputs `want` left out.  `lambda` is a Python keyword: the field
 # is `lambda_` (`want` takes either spelling)
 TaskSpaceDynamics = collections.namedtuple('TaskSpaceDynamics', ['jac', 'bias_acc', 'bias_torque', 'lambda_', 'tau', 'point', 'singular'])
+# what rollout_joint_dynamics returns: device tensors, None for the outputs `want` left out
+JointRollout = collections.namedtuple('JointRollout', ['q', 'qd', 'pos', 'singular'])
 LINK_ACCEL_MAX = 16   # DG_LINK_ACCEL_MAX: sensor-frame selectors of one link_accelerations call
 # what link_accelerations returns: [B, n, 3] views of ONE [B, n, 15] buffer, at the columns DG_LA_* of include/diygym_hip.h
 LinkAccelerations = collections.namedtuple('LinkAccelerations', ['lin_acc', 'ang_acc', 'specific_force', 'ang_vel', 'gravity'])
@@ -738,6 +743,79 @@ class HipBackend:
         self._dyn_check(self.lib.dg_world_task_space(self.handle, _ptr(self.state), body, frame, (ctypes.c_float * 3)(*lp.tolist()), mask, _ptr(q), _ptr(qd),
                                                      _ptr(acc), _ptr(tau_null), float(damping), *[_ptr(t) for t in out], self._stream()))
         return out
+
+    # -- forward dynamics and K-sample joint-space rollouts through the body's own model ---------------------------------------
+    def calculate_forward_dynamics(self, body, q=None, qd=None, tau=None, joint_damping=False, return_singular=False):
+        """``qdd = M(q)^-1 (tau - h(q, qd))`` for every env in ONE launch (``dg_world_forward_dynamics``): ``[B, nv]``, the inverse
+        of ``calculate_inverse_dynamics`` (rigid-body terms only).  ``q`` / ``qd`` default to each env's current values, ``tau``
+        to zero; with ``joint_damping`` the joints' URDF damping x ``qd`` comes off ``tau`` first, as in the step.  With
+        ``return_singular`` the result is ``(qdd, singular)``, ``singular`` ``[B]`` int32 (1: a pivot of M's factorisation sat at
+        the floor, see the C header).  Buffers kept per body and REUSED by the next call: clone what must last."""
+        body, _, nv = self._dyn_body(body)
+        q, qd, tau = self._rows_nv('q', q, nv), self._rows_nv('qd', qd, nv), self._rows_nv('tau', tau, nv)
+        qdd = self._dyn_buf('qdd', body, self.num_envs, nv)
+        sing = None
+        if return_singular:
+            key = ('fd_singular', body)
+            if key not in self._dyn_out:
+                self._dyn_out[key] = torch.zeros((self.num_envs, ), dtype=torch.int32, device=self.device)
+            sing = self._dyn_out[key]
+        self._dyn_check(self.lib.dg_world_forward_dynamics(self.handle, _ptr(self.state), body, _ptr(q), _ptr(qd), _ptr(tau), int(bool(joint_damping)), _ptr(qdd),
+                                                           _ptr(sing), self._stream()))
+        return (qdd, sing) if return_singular else qdd
+
+    def rollout_joint_dynamics(self, body, tau, q0=None, qd0=None, dt=None, frame=None, local_pos=(0.0, 0.0, 0.0), joint_damping=False, want=('q', 'qd')):
+        """``K`` candidate torque sequences per env rolled ``T`` steps through the body's rigid-body model in ONE launch
+        (``dg_world_rollout``): the inner loop of sampling MPC and shooting methods.  ``tau`` is ``[B, K, T, nv]`` float32 on this
+        device; sample ``k`` of env ``e`` starts at ``q0[e]``, ``qd0[e]`` (``[B, nv]`` or ``[nv]``; default: the env's current
+        values) and takes ``qdd = calculate_forward_dynamics(q, qd, tau[e, k, t])``, ``qd += dt qdd``, ``q += dt qd`` -- the step's
+        order; ``dt`` defaults to the scene's substep.  Returns a ``JointRollout``: ``q``, ``qd`` ``[B, K, T, nv]``, ``pos``
+        ``[B, K, T, 3]`` -- the world position of the point ``local_pos`` of the inertial frame of ``frame``'s link, as
+        ``calculate_jacobian`` takes it; ``'pos'`` in ``want`` needs ``frame`` -- and ``singular`` ``[B, K]`` int32; row ``t`` is
+        the state AFTER step ``t + 1``.  Fields not in ``want`` are None and cost nothing.  The env's per-env masses apply; the
+        state is not written.  A MODEL, not the step: no joint limits, motors, link damping or contacts.  The tensors are views
+        of buffers kept per ``(want, K, T)`` and REUSED by the next call: clone what must last.  ValueError, before anything is
+        launched, for everything the entry refuses and for tensors of the wrong shape, dtype or device."""
+        fields = JointRollout._fields
+        names = list(want)
+        if set(names) - set(fields):
+            raise ValueError('want must name some of %r, got %r' % (fields, want))
+        if 'pos' in names and frame is None:
+            raise ValueError("rollout_joint_dynamics: 'pos' in want needs frame")
+        if frame is not None and int(frame) < 0:
+            raise ValueError('frame must be a frame id >= 0, got %d' % int(frame))
+        body, frame, nv = self._dyn_body(body, -1 if frame is None else frame)
+        lp = np.asarray(local_pos, dtype=np.float32).reshape(-1)
+        if lp.size != 3:
+            raise ValueError('local_pos must have 3 elements, got %d' % lp.size)
+        if tau is None:
+            raise ValueError('dg_world_rollout: tau is NULL')
+        if not isinstance(tau, torch.Tensor) or tau.dim() != 4:
+            raise ValueError('tau must be a torch.Tensor of shape [B, K, T, nv]')
+        K, T = int(tau.shape[1]), int(tau.shape[2])
+        tau = self._require('tau', tau, (self.num_envs, K, T, nv), torch.float32)
+        q0, qd0 = self._rows_nv('q0', q0, nv), self._rows_nv('qd0', qd0, nv)
+        dt = float(self.layout.dt if dt is None else dt)
+        key = ('rollout', body, K, T, tuple(f in names for f in fields))
+        if key not in self._dyn_out:
+            B = self.num_envs
+            shapes = {'q': (B, K, T, nv), 'qd': (B, K, T, nv), 'pos': (B, K, T, 3), 'singular': (B, K)}
+            self._dyn_out[key] = JointRollout(*[torch.zeros(shapes[f], dtype=torch.int32 if f == 'singular' else torch.float32, device=self.device)
+                                                if f in names else None for f in fields])
+        out = self._dyn_out[key]
+        self._dyn_check(self.lib.dg_world_rollout(self.handle, _ptr(self.state), body, frame, (ctypes.c_float * 3)(*lp.tolist()), K, T, dt, int(bool(joint_damping)),
+                                                  _ptr(q0), _ptr(qd0), _ptr(tau), *[_ptr(t) for t in out], self._stream()))
+        return out
+
+    def rollout_grid(self, K):
+        """Diagnostic: the workgroups ``rollout_joint_dynamics`` launches for ``K`` samples per env (capped at the step's grid in the
+        global-workspace modes, whose workspace is sized for that grid; the kernel strides over the rest)."""
+        fn = self.lib.dg_debug_rollout_grid
+        fn.restype, fn.argtypes = ctypes.c_int32, [_vp, ctypes.c_int32]
+        n = fn(self.handle, int(K))
+        if n < 0:
+            raise ValueError(self.lib.dg_last_error().decode())
+        return n
 
     # -- the second half of p.getJointState(s): jointReactionForces, appliedJointMotorTorque ------------------------------------
     def joint_reaction_forces(self, body, joints=None):

@@ -22,6 +22,7 @@
 #include "dg_jointq.h"
 #include "dg_accelq.h"
 #include "dg_taskq.h"
+#include "dg_fdq.h"
 
 using namespace dg;
 
@@ -109,11 +110,16 @@ static dim3 grid_of(const dg_world* w) { const int per = envs_per_wave(w->lanes)
 // The tail of every entry that launches a kernel of DG_QUERY_KERNELS: the world's device, the mode's launcher of `member` with the
 // world's scene and motor table, `state` and `args` -- the kernel's parameters after `state` -- and what the launch left behind.
 template <class M, class... A>
-static int launch_args(const dg_world* w, void* stream, M LaunchTable::*member, const float* state, const A&... args) {
+static int launch_grid(const dg_world* w, dim3 grid, void* stream, M LaunchTable::*member, const float* state, const A&... args) {
   DG_ON_DEVICE(w->device);
-  (launch_table(w->lanes, w->mf).*member)(grid_of(w), w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), args...);
+  (launch_table(w->lanes, w->mf).*member)(grid, w->lds_bytes, (hipStream_t)stream, w->sc, w->mt, const_cast<float*>(state), args...);
   HIP_TRY(hipGetLastError());
   return DG_OK;
+}
+// ... on the step's grid, one env per lane: every kernel but the grid-stride rollout_kernel (dg_world_rollout)
+template <class M, class... A>
+static int launch_args(const dg_world* w, void* stream, M LaunchTable::*member, const float* state, const A&... args) {
+  return launch_grid(w, grid_of(w), stream, member, state, args...);
 }
 // ... for the kernels that end in the workspace pointer: every one but pose_kernel
 template <class M, class... A>
@@ -793,6 +799,56 @@ int32_t dg_world_task_space(dg_world* w, const float* state, int32_t body, int32
   if (taskq_slots(n, m) > w->sc.tr_slots) return slots_refusal(w, body, taskq_slots(n, m), "dg_world_task_space");
   return launch(w, stream, &LaunchTable::task_space, state, body, gf, local_pos[0], local_pos[1], local_pos[2], (int)axes_mask, q, qd, acc, tau_null, damping,
                 jac, bias_acc, bias_torque, lambda, tau, point, singular);
+}
+
+// ------------------------------------------------------------------ forward dynamics, joint-space rollouts (dg_fdq.h)
+int32_t dg_world_forward_dynamics(dg_world* w, const float* state, int32_t body, const float* q, const float* qd, const float* tau, int32_t joint_damping,
+                                  float* qdd, int32_t* singular, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_forward_dynamics")) return rc;
+  if (!qdd && !singular) return fail(DG_ERR_ARG, "dg_world_forward_dynamics: qdd and singular are both NULL");
+  const int n = body_row(w, body)[DG_BI_N_LINKS];
+  if (fdq_slots(n) > w->sc.tr_slots) return slots_refusal(w, body, fdq_slots(n), "dg_world_forward_dynamics");
+  return launch(w, stream, &LaunchTable::forward_dynamics, state, body, q, qd, tau, joint_damping != 0 ? 1 : 0, qdd, singular);
+}
+
+// workgroups of a dg_world_rollout of K samples per env: one item per lane; in the global-workspace modes no more than the step's
+// grid, which is what d_gws is sized for (rollout_kernel strides over the rest)
+static unsigned rollout_grid(const dg_world* w, int64_t K) {
+  const int64_t per = envs_per_wave(w->lanes), want = ((int64_t)w->num_envs * K + per - 1) / per, cap = (int64_t)grid_of(w).x;
+  if (w->lanes <= 0 && want > cap) return (unsigned)cap;
+  return (unsigned)(want > (int64_t)1 << 30 ? (int64_t)1 << 30 : want);  // (a grid dimension stays below 2^31; the kernel strides)
+}
+
+int32_t dg_world_rollout(dg_world* w, const float* state, int32_t body, int32_t frame, const float* local_pos, int32_t K, int32_t T, float dt, int32_t joint_damping,
+                         const float* q0, const float* qd0, const float* tau, float* q_out, float* qd_out, float* pos_out, int32_t* singular, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_rollout")) return rc;
+  if (K < 1) return fail(DG_ERR_ARG, "dg_world_rollout: K must be >= 1, got %d", K);
+  if (T < 1) return fail(DG_ERR_ARG, "dg_world_rollout: T must be >= 1, got %d", T);
+  if (!std::isfinite(dt) || !(dt > 0.f)) return fail(DG_ERR_ARG, "dg_world_rollout: dt must be finite and > 0, got %g", (double)dt);
+  if (!tau) return fail(DG_ERR_ARG, "dg_world_rollout: tau is NULL");
+  if (!q_out && !qd_out && !pos_out && !singular) return fail(DG_ERR_ARG, "dg_world_rollout: every output is NULL");
+  const int n = body_row(w, body)[DG_BI_N_LINKS];
+  {  // B K T n floats stay addressable in bytes
+    const int64_t lim = INT64_MAX / 4; int64_t v = w->num_envs;
+    for (const int64_t f : {(int64_t)K, (int64_t)T, (int64_t)n}) { if (v > lim / f) return fail(DG_ERR_ARG, "dg_world_rollout: %d envs x K %d x T %d x %d joints is beyond INT64_MAX / 4 values", w->num_envs, K, T, n); v *= f; }
+  }
+  int gf = -1; float lp[3] = {0.f, 0.f, 0.f};
+  if (pos_out) {
+    if (!local_pos) return fail(DG_ERR_ARG, "dg_world_rollout: local_pos is NULL (three host floats)");
+    if (frame < 0) return fail(DG_ERR_ARG, "dg_world_rollout: frame %d out of range (the base of a fixed body does not move)", frame);
+    if (const int rc = frame_check(w, body, frame, &gf, "dg_world_rollout")) return rc;
+    lp[0] = local_pos[0]; lp[1] = local_pos[1]; lp[2] = local_pos[2];
+  }
+  if (fdq_slots(n) > w->sc.tr_slots) return slots_refusal(w, body, fdq_slots(n), "dg_world_rollout");
+  return launch_grid(w, dim3(rollout_grid(w, K)), stream, &LaunchTable::rollout, state, body, gf, lp[0], lp[1], lp[2], (int)K, (int)T, dt, joint_damping != 0 ? 1 : 0,
+                     q0, qd0, tau, q_out, qd_out, pos_out, singular, w->d_gws);
+}
+
+// diagnostics: the workgroups dg_world_rollout would launch for K samples per env (tests: the cap of the global-workspace modes);
+// not part of the public header
+int32_t dg_debug_rollout_grid(const dg_world* w, int32_t K) {
+  if (!w || K < 1) return fail(DG_ERR_ARG, "dg_debug_rollout_grid: bad argument");
+  return (int32_t)rollout_grid(w, K);
 }
 
 // ------------------------------------------------------------------ closest-points query (dg_closestq.h)

@@ -21,6 +21,7 @@
 #include "dg_jointq.h"
 #include "dg_accelq.h"
 #include "dg_taskq.h"
+#include "dg_fdq.h"
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
 #include "dg_closestq.h"
 #endif

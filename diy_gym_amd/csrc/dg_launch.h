@@ -56,7 +56,11 @@ struct LaSelectors { int32_t n; float ghat[3]; dg_accel_selector s[DG_LINK_ACCEL
   X(link_accel, int body, const LaSelectors& sel, float* out, float* gws) \
   /* task-space dynamics (dg_taskq.h) */ \
   X(task_space, int body, int frame, float lx, float ly, float lz, int axes_mask, const float* q, const float* qd, const float* acc, const float* tau_null, \
-    float damping, float* jac, float* bias_acc, float* bias_torque, float* lambda, float* tau, float* point, int32_t* singular, float* gws)
+    float damping, float* jac, float* bias_acc, float* bias_torque, float* lambda, float* tau, float* point, int32_t* singular, float* gws) \
+  /* forward dynamics, joint-space rollouts (dg_fdq.h) */ \
+  X(forward_dynamics, int body, const float* q, const float* qd, const float* tau, int damp, float* qdd, int32_t* singular, float* gws) \
+  X(rollout, int body, int frame, float lx, float ly, float lz, int K, int T, float dt, int damp, const float* q0, const float* qd0, const float* tau, \
+    float* q_out, float* qd_out, float* pos_out, int32_t* singular, float* gws)
 
 struct LaunchTable {
   bool has_prof;

@@ -529,6 +529,39 @@ int32_t dg_world_task_space(dg_world* w, const float* state, int32_t body, int32
                             float* jac, float* bias_acc, float* bias_torque, float* lambda, float* tau, float* point, int32_t* singular,
                             void* stream);
 
+/* Forward dynamics of a fixed-base articulated body, every env at once, in ONE launch: qdd = M(q)^-1 (tau - h(q, qd)) with
+ * h = C qd - G, the rigid-body terms of dg_world_inverse_dynamics -- the two calls are inverses of each other.  Same bodies and
+ * rules as the dynamics queries: device float32 arrays, nothing allocated, freed or synchronised.
+ *   q, qd, tau     [num_envs][nv] or NULL = the env's own q, qd; a NULL tau is zero (a NULL call and a call given the same numbers
+ *                  are the same bits)
+ *   joint_damping  != 0: tau is first reduced by the joints' URDF damping x qd, the term the step applies
+ *   qdd            [num_envs][nv]
+ *   singular       [num_envs] int32, nullable: 1 when a pivot of the Cholesky factorisation of M was <= 1e-5 x its own diagonal
+ *                  entry of M (dg_world_task_space's rule); the pivot is then that floor, so qdd stays finite
+ * DG_ERR_ARG (nothing launched, outputs untouched) for what the dynamics queries refuse, qdd and singular both NULL, and a body
+ * whose pass would need more workspace than the world has. */
+int32_t dg_world_forward_dynamics(dg_world* w, const float* state, int32_t body, const float* q, const float* qd, const float* tau,
+                                  int32_t joint_damping, float* qdd, int32_t* singular, void* stream);
+
+/* K candidate torque sequences per env rolled T steps through the body's own rigid-body model, in ONE launch: the inner loop of
+ * sampling MPC and shooting methods.  Sample k of env e starts at q0[e], qd0[e] (NULL: the env's own) and for t = 0 .. T-1 takes
+ * qdd = dg_world_forward_dynamics(q, qd, tau[e][k][t]) and integrates semi-implicitly, the step's order: qd += dt qdd; q += dt qd.
+ * Row t of every output is the state AFTER step t + 1.  The env's own per-env masses apply; the state is read, never written.  A
+ * MODEL of the arm, not the step: no joint limits, motors, link damping or contacts.
+ *   frame, local_pos   the point whose world position pos_out reports: local_pos[3] (HOST floats) in the INERTIAL frame of the link
+ *                      of `frame` (the body's pybullet joint index), as dg_world_jacobian takes it; read only when pos_out is set
+ *   tau                [num_envs][K][T][nv], required
+ *   q_out, qd_out      [num_envs][K][T][nv]
+ *   pos_out            [num_envs][K][T][3], at the NEW q of each step
+ *   singular           [num_envs][K] int32: 1 when any step of the sample held a pivot at the floor
+ * Each output may be NULL, at least one must not be.  DG_ERR_ARG (nothing launched, outputs untouched) for what the dynamics queries
+ * refuse, K < 1, T < 1, a dt that is not finite or <= 0, tau NULL, every output NULL, num_envs x K x T x nv beyond INT64_MAX / 4,
+ * with pos_out a NULL local_pos or a frame the body does not have, and a body whose pass would need more workspace than the world
+ * has. */
+int32_t dg_world_rollout(dg_world* w, const float* state, int32_t body, int32_t frame, const float* local_pos, int32_t K, int32_t T,
+                         float dt, int32_t joint_damping, const float* q0, const float* qd0, const float* tau,
+                         float* q_out, float* qd_out, float* pos_out, int32_t* singular, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
