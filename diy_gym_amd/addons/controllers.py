@@ -387,6 +387,151 @@ class MppiController(Addon):
         sim.apply_joint_torque(self.uid, self._clip(torque) if self.clip_torque else torque)
 
 
+def lqr_discretise(A_q, A_v, Minv, h, substeps):
+    """``(A [.., 2 nv, 2 nv], B [.., 2 nv, nv])`` of the linearised joint dynamics ``qdd = A_q dq + A_v qd + Minv dtau`` over one env
+    step of ``substeps`` substeps of ``h`` seconds with the torque held, state ``[dq; qd]``.  Per substep, the step's semi-implicit
+    order (``qd += h qdd; q += h qd``): ``A_h = [[I + h^2 A_q, h (I + h A_v)], [h A_q, I + h A_v]]``, ``B_h = [[h^2 Minv], [h Minv]]``;
+    then ``A = A_h^s``, ``B = sum_{k < s} A_h^k B_h``."""
+    nv = A_q.shape[-1]
+    I = torch.eye(nv, dtype=A_q.dtype, device=A_q.device).expand_as(A_q)
+    v = I + h * A_v
+    Ah = torch.cat([torch.cat([I + h * h * A_q, h * v], dim=-1), torch.cat([h * A_q, v], dim=-1)], dim=-2)
+    Bh = torch.cat([h * h * Minv, h * Minv], dim=-2)
+    Ak, B = torch.eye(2 * nv, dtype=A_q.dtype, device=A_q.device).expand_as(Ah), torch.zeros_like(Bh)
+    for _ in range(int(substeps)):
+        B = B + Ak @ Bh
+        Ak = Ak @ Ah
+    return Ak, B
+
+
+def lqr_gain(A, B, Q, R, horizon):
+    """``K [.., nv, 2 nv]`` after ``horizon`` backward Riccati iterations from ``P = Q``: ``K = (R + B^T P B)^-1 B^T P A``,
+    ``P = Q + A^T P (A - B K)``."""
+    P = Q.expand_as(A)
+    K = torch.zeros_like(B.transpose(-1, -2))
+    At, Bt = A.transpose(-1, -2), B.transpose(-1, -2)
+    for _ in range(int(horizon)):
+        BtP = Bt @ P
+        K = torch.linalg.solve(R + BtP @ B, BtP @ A)
+        P = Q + At @ P @ (A - B @ K)
+    return K
+
+
+class LqrController(Addon):
+    """Joint-space LQR about a joint target ``q*`` that persists per env, written ONLY on the ``env.sim`` query contract: a hook
+    addon, no ``compile()`` op, no counterpart in the reference.  The arm's model is linearised at ``(q*, 0, tau_g(q*))`` with
+    joint damping on by ONE ``forward_dynamics_derivatives`` launch (analytic first derivatives), discretised over the env step in
+    the step's semi-implicit order (``lqr_discretise``) and the gain comes from ``horizon`` backward Riccati iterations in batched
+    torch (``lqr_gain``, in float64); then ``tau = tau_g(q*) - K [q - q*; qd]``.
+
+    Configs: ``target`` (``[nv]``; default: the pose the reset left -- the model's rest or reset pose), ``q_weight`` (1000; a scalar
+    or ``[nv]``), ``qd_weight`` (10; the same), ``torque_weight`` (0.001; the same), ``horizon`` (100), ``relinearize`` (10: the gains
+    are recomputed at reset, in ``set_target`` and every that many steps), ``clip_torque`` (yes: the torque is clamped to the URDF
+    effort limits).
+
+    The action ``target`` [nv] in ``Box(+-0.05)`` is ADDED to ``q*``; ``set_target(q, mask)`` sets it directly.  Per tick:
+    ``calculate_inverse_dynamics(q*, qd=0)`` (the gravity compensation at the target), ``joint_states`` and
+    ``apply_joint_torque`` -- three launches -- and every ``relinearize`` ticks one ``forward_dynamics_derivatives`` launch between
+    the first two.  The model has no joint limits, motors, link damping or contacts, and the gain is that of the target's
+    neighbourhood: far from ``q*`` it is a stiff PD law with gravity compensation, nothing more.
+
+    ``reset()`` switches the body's default velocity motors off once and, for the envs in ``env.reset_mask``, puts ``q*`` back at
+    ``target`` and marks the gains stale.  Without a ``target`` it marks those envs' ``q*`` stale instead, and the first tick AFTER the
+    reset reads it from ``joint_states`` -- a hook's ``reset()`` runs before the scene's reset ops, so the pose the reset leaves (a
+    ``joint_controller``'s ``rest_position``, say) is not there yet; that tick's joint-state launch comes first, the count is the same.
+    Until that tick ``q_star`` holds the earlier target."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        if not hasattr(parent, 'robot'):
+            raise ValueError('lqr_controller goes on a model, not on the environment')
+        self.uid = parent.uid
+        robot = parent.robot
+        self.nv = nv = robot.num_dofs
+        if nv < 1:
+            raise ValueError('lqr_controller: the model has no joints')
+
+        def vec(key, default):
+            v = np.asarray(config.get(key, default), dtype=np.float64).reshape(-1)
+            if v.size not in (1, nv):
+                raise ValueError('lqr_controller: %s must be a number or have %d elements, got %d' % (key, nv, v.size))
+            return np.broadcast_to(v, (nv, )).copy()
+        self.target = None if 'target' not in config else [float(v) for v in config.get('target')]
+        if self.target is not None and len(self.target) != nv:
+            raise ValueError('lqr_controller: target must have %d elements, got %d' % (nv, len(self.target)))
+        self.q_weight, self.qd_weight, self.torque_weight = vec('q_weight', 1000.0), vec('qd_weight', 10.0), vec('torque_weight', 0.001)
+        if self.q_weight.min() < 0 or self.qd_weight.min() < 0:
+            raise ValueError('lqr_controller: q_weight and qd_weight must be >= 0')
+        if not self.torque_weight.min() > 0:
+            raise ValueError('lqr_controller: torque_weight must be > 0')
+        self.horizon, self.relinearize = int(config.get('horizon', 100)), int(config.get('relinearize', 10))
+        if self.horizon < 1 or self.relinearize < 1:
+            raise ValueError('lqr_controller: horizon and relinearize must be >= 1, got %d and %d' % (self.horizon, self.relinearize))
+        self.clip_torque = bool(config.get('clip_torque', True))
+        self.torque_limit = [float(j.effort) for j in robot.joints if j.q_index > -1]   # in q_index order
+        self.action_space = spaces.Dict(OrderedDict(target=spaces.Box(-0.05, 0.05, shape=(nv, ), dtype='float32')))
+        self._ready = False
+
+    def reset(self):
+        env = self.env
+        sim, L = env.sim, env.layout
+        B, nv = sim.num_envs, self.nv
+        if not self._ready:
+            first = L.body_first_link[L.resolve_frame(self.uid, -1)[0]]
+            cfg = sim.motor_cfg()
+            cfg[[first + i for i in range(nv)], 2] = 0.0   # the default velocity motors off
+            sim.set_motor_cfg(cfg)
+            self._effort = torch.tensor(self.torque_limit, dtype=torch.float32, device=sim.device)
+            self._Q = torch.diag(torch.tensor(np.concatenate([self.q_weight, self.qd_weight]), dtype=torch.float64, device=sim.device))
+            self._R = torch.diag(torch.tensor(self.torque_weight, dtype=torch.float64, device=sim.device))
+            self._zero = torch.zeros((B, nv), dtype=torch.float32, device=sim.device)
+            self.q_star = torch.zeros((B, nv), dtype=torch.float32, device=sim.device)
+            self.gain = torch.zeros((B, nv, 2 * nv), dtype=torch.float32, device=sim.device)
+            self._stale = torch.zeros((B, 1), dtype=torch.bool, device=sim.device)
+            self._any_stale = False
+            self._ready = True
+        rows = torch.ones((B, 1), dtype=torch.bool, device=sim.device) if env.reset_mask is None else torch.as_tensor(env.reset_mask, device=sim.device).reshape(B, 1) != 0
+        if self.target is not None:
+            self.q_star = torch.where(rows, torch.tensor(self.target, dtype=torch.float32, device=sim.device).expand(B, nv), self.q_star)
+        else:   # a hook's reset() runs BEFORE the scene's reset ops: the pose the reset leaves is read on the next tick
+            self._stale = self._stale | rows
+            self._any_stale = True
+        self._since = None   # the next tick linearises
+
+    def set_target(self, q, mask=None):
+        """The joint target of the envs ``mask`` selects (None: all): ``q`` ``[B, nv]`` or ``[nv]``.  The gains are recomputed on
+        the next tick."""
+        sim = self.env.sim
+        rows = torch.ones((sim.num_envs, 1), dtype=torch.bool, device=sim.device) if mask is None else torch.as_tensor(mask, device=sim.device).reshape(sim.num_envs, 1) != 0
+        self.q_star = torch.where(rows, self.env._as_batch(q, self.nv), self.q_star)
+        self._stale = self._stale & ~rows
+        self._since = None
+
+    def _clip(self, tau):
+        return torch.where(self._effort > 0, torch.minimum(torch.maximum(tau, -self._effort), self._effort), tau)
+
+    def update(self, action):
+        env = self.env
+        sim, L = env.sim, env.layout
+        state = None
+        if self._any_stale:   # the first tick after a reset: the target of the envs it reset is the pose it left (this tick's one joint-state launch)
+            state = tuple(t.clone() for t in sim.joint_states(self.uid))
+            self.q_star = torch.where(self._stale, state[0], self.q_star)
+            self._stale = torch.zeros_like(self._stale)
+            self._any_stale = False
+        self.q_star = (self.q_star + env._as_batch(action['target'], self.nv)).contiguous()
+        tau_g = sim.calculate_inverse_dynamics(self.uid, q=self.q_star, qd=self._zero)
+        if self._since is None or self._since >= self.relinearize:
+            d = sim.forward_dynamics_derivatives(self.uid, self.q_star, self._zero, tau_g, joint_damping=True, want=('dqdd_dq', 'dqdd_dqd', 'dqdd_dtau'))
+            A, Bm = lqr_discretise(d.dqdd_dq.double(), d.dqdd_dqd.double(), d.dqdd_dtau.double(), float(L.dt), int(L.substeps))
+            self.gain = lqr_gain(A, Bm, self._Q, self._R, self.horizon).float()
+            self._since = 0
+        self._since += 1
+        q, qd = sim.joint_states(self.uid) if state is None else state
+        x = torch.cat([q - self.q_star, qd], dim=1)
+        tau = tau_g - (self.gain @ x[:, :, None])[:, :, 0]
+        sim.apply_joint_torque(self.uid, self._clip(tau) if self.clip_torque else tau)
+
+
 class ExternalForce(_Controller):
     """World-frame force on the base for the next step (reference:
     diy_gym/addons/controllers/external_force.py:9-24).  ``xyz`` is passed as

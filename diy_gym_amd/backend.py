@@ -75,6 +75,7 @@ SYMBOLS = {
     'dg_world_forward_dynamics': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
     'dg_world_rollout': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                           ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_dynamics_derivatives': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
     'dg_world_closest': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -136,6 +137,8 @@ JOINT_WRENCH_MAX = 16   # DG_JOINT_WRENCH_MAX: joint selectors of one joint_reac
 TaskSpaceDynamics = collections.namedtuple('TaskSpaceDynamics', ['jac', 'bias_acc', 'bias_torque', 'lambda_', 'tau', 'point', 'singular'])
 # what rollout_joint_dynamics returns: device tensors, None for the outputs `want` left out
 JointRollout = collections.namedtuple('JointRollout', ['q', 'qd', 'pos', 'singular'])
+# what forward_dynamics_derivatives returns: device tensors, None for the outputs `want` left out
+DynamicsDerivatives = collections.namedtuple('DynamicsDerivatives', ['qdd', 'dqdd_dq', 'dqdd_dqd', 'dqdd_dtau', 'dtau_dq', 'dtau_dqd', 'singular'])
 LINK_ACCEL_MAX = 16   # DG_LINK_ACCEL_MAX: sensor-frame selectors of one link_accelerations call
 # what link_accelerations returns: [B, n, 3] views of ONE [B, n, 15] buffer, at the columns DG_LA_* of include/diygym_hip.h
 LinkAccelerations = collections.namedtuple('LinkAccelerations', ['lin_acc', 'ang_acc', 'specific_force', 'ang_vel', 'gravity'])
@@ -816,6 +819,90 @@ class HipBackend:
         if n < 0:
             raise ValueError(self.lib.dg_last_error().decode())
         return n
+
+    # -- derivatives of the forward dynamics, and the forward dynamics as an autograd function ---------------------------------
+    def _points_nv(self, name, v, nv):
+        """``v`` for ``forward_dynamics_derivatives``: ``(tensor or None, P or None)``; ``[nv]`` and ``[B, nv]`` are one point per
+        env, ``[B, P, nv]`` is P."""
+        if v is None:
+            return None, None
+        if isinstance(v, torch.Tensor) and v.dim() == 3:
+            return self._require(name, v, (self.num_envs, int(v.shape[1]), nv), torch.float32), int(v.shape[1])
+        return self._rows_nv(name, v, nv), None
+
+    def forward_dynamics_derivatives(self, body, q=None, qd=None, tau=None, joint_damping=False, want=('dqdd_dq', 'dqdd_dqd', 'dqdd_dtau')):
+        """The derivatives of ``calculate_forward_dynamics`` for every env, at ``P`` points per env, in ONE launch
+        (``dg_world_dynamics_derivatives``): what LQR, iLQR / DDP and an EKF linearise with.  Returns a ``DynamicsDerivatives``:
+        ``qdd`` (the call's own ``calculate_forward_dynamics`` result), ``dqdd_dq``, ``dqdd_dqd`` (``[i][j]``: d qdd_i / d q_j, d qd_j),
+        ``dqdd_dtau = M^-1``, ``dtau_dq``, ``dtau_dqd`` (the derivatives of the inverse dynamics at fixed ``qdd``, the second with
+        the damping diagonal when ``joint_damping``; ``dqdd_dq = -M^-1 dtau_dq``) and ``singular`` int32.  Inputs ``[B, nv]`` or
+        ``[nv]`` give matrices ``[B, nv, nv]``, ``qdd [B, nv]`` and ``singular [B]``; inputs ``[B, P, nv]`` (all given inputs must
+        agree on ``P``; a ``[B, nv]`` or ``[nv]`` input cannot be mixed with them) give ``[B, P, nv, nv]``, ``[B, P, nv]`` and
+        ``[B, P]``.  ``q`` / ``qd`` default to each env's current values, ``tau`` to zero, at every point.  The derivatives are
+        analytic, first order only.  Fields not in ``want`` are None and cost nothing.  The env's per-env masses apply; the state
+        is not written.  The tensors are buffers kept per ``(body, want, P)`` and REUSED by the next call: clone what must last.
+        ValueError, before anything is launched, for everything the entry refuses and for tensors of the wrong shape, dtype or
+        device."""
+        fields = DynamicsDerivatives._fields
+        names = list(want)
+        if set(names) - set(fields):
+            raise ValueError('want must name some of %r, got %r' % (fields, want))
+        body, _, nv = self._dyn_body(body)
+        ins = [self._points_nv(name, v, nv) for name, v in (('q', q), ('qd', qd), ('tau', tau))]
+        given = [(name, P) for name, (t, P) in zip(('q', 'qd', 'tau'), ins) if t is not None]
+        Ps = set(P for _, P in given)
+        if len(Ps) > 1:
+            raise ValueError('forward_dynamics_derivatives: the inputs must agree on the points per env, got %s'
+                             % ', '.join('%s %s' % (name, 'one point [B, nv]' if P is None else 'P = %d' % P) for name, P in given))
+        P = Ps.pop() if Ps else None
+        B, n_pts = self.num_envs, 1 if P is None else P
+        key = ('ddq', body, P, tuple(f in names for f in fields))
+        fresh = False
+        if key not in self._dyn_out:
+            lead = (B, ) if P is None else (B, P)
+            shapes = dict({f: lead + (nv, nv) for f in fields}, qdd=lead + (nv, ), singular=lead)
+            self._dyn_out[key] = DynamicsDerivatives(*[torch.zeros(shapes[f], dtype=torch.int32 if f == 'singular' else torch.float32, device=self.device)
+                                                       if f in names else None for f in fields])
+            fresh = True
+        out = self._dyn_out[key]
+        try:
+            self._dyn_check(self.lib.dg_world_dynamics_derivatives(self.handle, _ptr(self.state), body, n_pts, *[_ptr(t) for t, _ in ins], int(bool(joint_damping)),
+                                                                   *[_ptr(t) for t in out], self._stream()))
+        except ValueError:
+            if fresh:   # a refused call keeps no buffers
+                del self._dyn_out[key]
+            raise
+        return out
+
+    def forward_dynamics_fn(self, body, joint_damping=False):
+        """``f(q, qd, tau) -> qdd``: ``calculate_forward_dynamics`` as a ``torch.autograd.Function``, so that ``loss.backward()`` goes
+        through the body's rigid-body model.  ``q``, ``qd``, ``tau`` are ``[B, nv]`` or ``[B, P, nv]`` float32 tensors on this
+        device.  Forward is ONE ``forward_dynamics_derivatives`` launch: it returns a fresh ``qdd`` and saves clones of the three
+        ``dqdd_*`` matrices; backward is three batched products, ``g_q = dqdd_dq^T g``, ``g_qd = dqdd_dqd^T g``,
+        ``g_tau = dqdd_dtau^T g``, only for the inputs that need a gradient (the others' matrices are not computed).  FIRST derivatives only:
+        the saved matrices are constants of the graph, and ``backward`` is marked ``once_differentiable``, so asking for a gradient of a
+        gradient through ``f`` raises instead of returning zero."""
+        sim = self
+        damping = bool(joint_damping)
+
+        class ForwardDynamics(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, q, qd, tau):
+                need = tuple(ctx.needs_input_grad[:3])   # only the matrices backward will read are computed, cloned and saved
+                d = sim.forward_dynamics_derivatives(body, q.detach().contiguous(), qd.detach().contiguous(), tau.detach().contiguous(), damping,
+                                                     want=('qdd', ) + tuple(f for f, n in zip(('dqdd_dq', 'dqdd_dqd', 'dqdd_dtau'), need) if n))
+                ctx.need = need
+                ctx.save_for_backward(*[m.clone() for m, n in zip((d.dqdd_dq, d.dqdd_dqd, d.dqdd_dtau), need) if n])
+                return d.qdd.clone()
+
+            @staticmethod
+            @torch.autograd.function.once_differentiable
+            def backward(ctx, g):
+                mats = iter(ctx.saved_tensors)
+                g = g.contiguous().unsqueeze(-2)   # [.., 1, nv] x [.., nv, nv] -> g^T J = (J^T g)^T
+                return tuple(torch.matmul(g, next(mats)).squeeze(-2) if n else None for n in ctx.need)
+
+        return ForwardDynamics.apply
 
     # -- the second half of p.getJointState(s): jointReactionForces, appliedJointMotorTorque ------------------------------------
     def joint_reaction_forces(self, body, joints=None):

@@ -23,6 +23,7 @@
 #include "dg_accelq.h"
 #include "dg_taskq.h"
 #include "dg_fdq.h"
+#include "dg_ddq.h"
 
 using namespace dg;
 
@@ -849,6 +850,23 @@ int32_t dg_world_rollout(dg_world* w, const float* state, int32_t body, int32_t 
 int32_t dg_debug_rollout_grid(const dg_world* w, int32_t K) {
   if (!w || K < 1) return fail(DG_ERR_ARG, "dg_debug_rollout_grid: bad argument");
   return (int32_t)rollout_grid(w, K);
+}
+
+// ------------------------------------------------------------------ forward-dynamics derivatives (dg_ddq.h)
+int32_t dg_world_dynamics_derivatives(dg_world* w, const float* state, int32_t body, int32_t P, const float* q, const float* qd, const float* tau, int32_t joint_damping,
+                                      float* qdd, float* dqdd_dq, float* dqdd_dqd, float* dqdd_dtau, float* dtau_dq, float* dtau_dqd, int32_t* singular, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_dynamics_derivatives")) return rc;
+  if (P < 1) return fail(DG_ERR_ARG, "dg_world_dynamics_derivatives: P must be >= 1, got %d", P);
+  if (!qdd && !dqdd_dq && !dqdd_dqd && !dqdd_dtau && !dtau_dq && !dtau_dqd && !singular) return fail(DG_ERR_ARG, "dg_world_dynamics_derivatives: every output is NULL");
+  const int n = body_row(w, body)[DG_BI_N_LINKS];
+  {  // B P n n floats stay addressable in bytes
+    const int64_t lim = INT64_MAX / 4; int64_t v = w->num_envs;
+    for (const int64_t f : {(int64_t)P, (int64_t)n, (int64_t)n}) { if (v > lim / f) return fail(DG_ERR_ARG, "dg_world_dynamics_derivatives: %d envs x P %d x %d x %d joints is beyond INT64_MAX / 4 values", w->num_envs, P, n, n); v *= f; }
+  }
+  if (n > DDQ_MAX_JOINTS) return fail(DG_ERR_ARG, "dg_world_dynamics_derivatives: body %d has %d joints, the derivatives take at most %d", body, n, DDQ_MAX_JOINTS);
+  if (ddq_slots(n) > w->sc.tr_slots) return slots_refusal(w, body, ddq_slots(n), "dg_world_dynamics_derivatives");
+  return launch_grid(w, dim3(rollout_grid(w, P)), stream, &LaunchTable::dynamics_derivatives, state, body, (int)P, q, qd, tau, joint_damping != 0 ? 1 : 0,
+                     qdd, dqdd_dq, dqdd_dqd, dqdd_dtau, dtau_dq, dtau_dqd, singular, w->d_gws);
 }
 
 // ------------------------------------------------------------------ closest-points query (dg_closestq.h)

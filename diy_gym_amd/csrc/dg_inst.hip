@@ -22,6 +22,7 @@
 #include "dg_accelq.h"
 #include "dg_taskq.h"
 #include "dg_fdq.h"
+#include "dg_ddq.h"
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
 #include "dg_closestq.h"
 #endif

@@ -60,7 +60,10 @@ struct LaSelectors { int32_t n; float ghat[3]; dg_accel_selector s[DG_LINK_ACCEL
   /* forward dynamics, joint-space rollouts (dg_fdq.h) */ \
   X(forward_dynamics, int body, const float* q, const float* qd, const float* tau, int damp, float* qdd, int32_t* singular, float* gws) \
   X(rollout, int body, int frame, float lx, float ly, float lz, int K, int T, float dt, int damp, const float* q0, const float* qd0, const float* tau, \
-    float* q_out, float* qd_out, float* pos_out, int32_t* singular, float* gws)
+    float* q_out, float* qd_out, float* pos_out, int32_t* singular, float* gws) \
+  /* forward-dynamics derivatives (dg_ddq.h) */ \
+  X(dynamics_derivatives, int body, int P, const float* q, const float* qd, const float* tau, int damp, float* qdd, float* dqdd_dq, float* dqdd_dqd, float* dqdd_dtau, \
+    float* dtau_dq, float* dtau_dqd, int32_t* singular, float* gws)
 
 struct LaunchTable {
   bool has_prof;

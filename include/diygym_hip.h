@@ -562,6 +562,28 @@ int32_t dg_world_rollout(dg_world* w, const float* state, int32_t body, int32_t 
                          float dt, int32_t joint_damping, const float* q0, const float* qd0, const float* tau,
                          float* q_out, float* qd_out, float* pos_out, int32_t* singular, void* stream);
 
+/* The derivatives of dg_world_forward_dynamics at P points per env, in ONE launch of num_envs x P work items: what LQR, iLQR / DDP,
+ * an EKF and backpropagation through the model linearise with.  With d the joints' URDF damping when joint_damping != 0, else
+ * zero, and ID the rigid-body inverse dynamics of dg_world_inverse_dynamics, per point:
+ *   qdd        [num_envs][P][nv]      M^-1 (tau - d o qd - h(q, qd)): dg_world_forward_dynamics' result, bit for bit
+ *   dqdd_dq    [num_envs][P][nv][nv]  -M^-1 dtau_dq        row-major, [i][j] = d qdd_i / d q_j
+ *   dqdd_dqd   [num_envs][P][nv][nv]  -M^-1 dtau_dqd
+ *   dqdd_dtau  [num_envs][P][nv][nv]   M^-1
+ *   dtau_dq    [num_envs][P][nv][nv]  d ID_i(q, qd, qdd) / d q_j at FIXED qdd
+ *                                     (the point is qdd refined once against the inverse-dynamics residual, in the workspace: the
+ *                                     qdd output keeps dg_world_forward_dynamics' bits, whose fp32 error grows with cond(M))
+ *   dtau_dqd   [num_envs][P][nv][nv]  d ID_i / d qd_j + d_i delta_ij
+ *   singular   [num_envs][P] int32    dg_world_forward_dynamics' flag
+ * The derivatives are analytic (a forward-mode tangent of the Newton-Euler passes), never finite differences; first derivatives only.
+ *   q, qd, tau [num_envs][P][nv] or NULL = the env's own q, qd, zero torque, at every point of that env
+ * Each output may be NULL and then costs nothing; at least one must not be.  The state is read, never written; the env's own per-env
+ * masses apply.  DG_ERR_ARG (nothing launched, outputs untouched) for what dg_world_forward_dynamics refuses, P < 1, every output
+ * NULL, num_envs x P x nv x nv beyond INT64_MAX / 4, a body of more than 64 joints, and a body whose pass would need more workspace
+ * than the world has (33 nv slots of the transient region). */
+int32_t dg_world_dynamics_derivatives(dg_world* w, const float* state, int32_t body, int32_t P, const float* q, const float* qd, const float* tau,
+                                      int32_t joint_damping, float* qdd, float* dqdd_dq, float* dqdd_dqd, float* dqdd_dtau,
+                                      float* dtau_dq, float* dtau_dqd, int32_t* singular, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
