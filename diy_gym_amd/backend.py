@@ -81,6 +81,7 @@ SYMBOLS = {
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_set_render_diag': (ctypes.c_int32, [_vp, ctypes.c_int32]),
     'dg_world_set_diag_buffer': (ctypes.c_int32, [_vp, _vp]),
+    'dg_world_set_skip_counter': (ctypes.c_int32, [_vp, _vp]),
     'dg_world_set_profile_buffer': (ctypes.c_int32, [_vp, _vp]),
     'dg_debug_plan': (ctypes.c_int32, [_c_i32p, ctypes.c_int64, _c_f64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _c_i32p, _c_i32p,
                                        ctypes.c_int64]),
@@ -1355,6 +1356,16 @@ class HipBackend:
 
     def disable_diagnostics(self):
         self._check(self.lib.dg_world_set_diag_buffer(self.handle, None))
+
+    def enable_skip_counter(self):
+        """int32 [num_envs]: with every step, how many of its substeps ran without narrow phase and pose pass (the clearance
+        measured by the previous narrow phase exceeded what the arms could have moved; dg_world_set_skip_counter)."""
+        self.skipped = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self._check(self.lib.dg_world_set_skip_counter(self.handle, _ptr(self.skipped)))
+        return self.skipped
+
+    def disable_skip_counter(self):
+        self._check(self.lib.dg_world_set_skip_counter(self.handle, None))
 
     @property
     def kernel_name(self):

@@ -200,7 +200,7 @@ int32_t dg_world_create(const int32_t* I, int64_t n_i, const double* F, int64_t 
   sc.BF = dF + I[DG_H_OFF_BODY_F]; sc.LF = dF + I[DG_H_OFF_LINK_F]; sc.FF = dF + I[DG_H_OFF_FRAME_F]; sc.SF = dF + I[DG_H_OFF_SHAPE_F];
   sc.PF = dF + I[DG_H_OFF_POINT_F]; sc.OF = dF + I[DG_H_OFF_OP_F]; sc.FL = dF + I[DG_H_OFF_FLIST]; sc.HF = dF;
   sc.KI = dI + I[DG_H_OFF_CONS_I]; sc.KF = dF + I[DG_H_OFF_CONS_F];
-  sc.PLB = (cip)w->d_plan; sc.PLL = sc.PLB + (size_t)sc.nb * PLB_STRIDE; sc.PD = sc.PLB + p.pd_off; sc.GD = (cfp)(sc.PLB + p.gd_off); sc.SD = sc.PLB + p.sd_off; sc.AM = sc.PLB + p.am_off;
+  sc.PLB = (cip)w->d_plan; sc.PLL = sc.PLB + (size_t)sc.nb * PLB_STRIDE; sc.PD = sc.PLB + p.pd_off; sc.GD = (cfp)(sc.PLB + p.gd_off); sc.SD = sc.PLB + p.sd_off; sc.AM = sc.PLB + p.am_off; sc.RH = (cfp)(sc.PLB + p.rh_off);
   sc.hull_ws = w->d_hull_ws;
   // cameras: per-env shape/camera pose table written by pose_kernel, read by render_kernel
   w->ncam = I[DG_H_N_CAMERAS]; w->d_CI = dI + I[DG_H_OFF_CAMERA_I]; w->d_CF = dF + I[DG_H_OFF_CAMERA_F]; w->d_PLN = dF + I[DG_H_OFF_PLANE_F];
@@ -230,6 +230,7 @@ int32_t dg_debug_plan(const int32_t* I, int64_t n_i, const double* F, int64_t n_
   out[DG_PLAN_GWS_FLOATS] = clamp(p.gws_floats); out[DG_PLAN_HULL_WS_FLOATS] = clamp(p.hull_ws_floats); out[DG_PLAN_NBA] = sc.nba; out[DG_PLAN_NSHA] = sc.nsha;
   out[DG_PLAN_AB_STRIDE] = sc.ab_stride; out[DG_PLAN_PD_OFF] = clamp(p.pd_off); out[DG_PLAN_GD_OFF] = clamp(p.gd_off); out[DG_PLAN_SD_OFF] = clamp(p.sd_off);
   out[DG_PLAN_AM_OFF] = clamp(p.am_off); out[DG_PLAN_TABLE_WORDS] = clamp(p.table.size());
+  out[DG_PLAN_NP_SKIP] = sc.np_skip; out[DG_PLAN_RH_OFF] = clamp(p.rh_off);
   if (table) memcpy(table, p.table.data(), sizeof(int32_t) * std::min<size_t>(p.table.size(), (size_t)std::max<int64_t>(table_cap, 0)));
   return DG_OK;
 }
@@ -261,6 +262,7 @@ int32_t dg_world_set_motor_cfg(dg_world* w, const double* cfg) {
   return DG_OK;
 }
 int32_t dg_world_set_diag_buffer(dg_world* w, int32_t* diag) { if (!w) return fail(DG_ERR_ARG, "null world"); w->diag = diag; return DG_OK; }
+int32_t dg_world_set_skip_counter(dg_world* w, int32_t* skipped) { if (!w) return fail(DG_ERR_ARG, "null world"); w->sc.skip_count = skipped; return DG_OK; }
 
 int32_t dg_world_init_state(dg_world* w, float* state, void* stream) {
   if (!w || !state) return fail(DG_ERR_ARG, "null argument");

@@ -72,6 +72,11 @@ struct DevScene {
   uint64_t seed; int64_t env_base;
   float h, gx, gy, gz;
   float hm;  // time base of a motor row's impulse bound: h x DG_HF_MOTOR_IMPULSE_SCALE (the substep, or the full step)
+  // helper-wave kernel, contact-free regime: a substep k >= 1 leaves out its narrow phase and the pose pass in front of it when the
+  // clearance the previous narrow phase measured exceeds what the arms can have moved since (substep_np_skip, dg_solver.h)
+  int32_t np_skip;
+  cfp RH;   // per link, device-only (np_skip): rho, the farthest any point of any shape on this or a later link of the chain can be from the joint's origin
+  int32_t* skip_count;  // dg_world_set_skip_counter: per env, the substeps of the last step that were skipped; or null
 };
 struct MotorTable { float v[DG_MAX_LINKS * 3]; };  // kp, kd, max_force (<0 raw impulse)
 

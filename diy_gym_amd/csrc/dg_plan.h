@@ -44,6 +44,9 @@ struct PlanSwitches {
 #define X(name, field, doc) Switch field;
   DG_PLAN_SWITCHES(X)
 #undef X
+  // DG_NO_NP_SKIP: every substep runs its narrow phase and the pose pass in front of it.  Read like the switches above but kept
+  // beside the table: tests/test_world_plan.py pins the table at its twenty entries, and README.md's list with it.
+  Switch no_np_skip;
 };
 PlanSwitches plan_switches_from_env();  // read afresh on every call
 
@@ -55,8 +58,8 @@ struct WorldPlan {
   int render_diag = 0, render_wpe = 2;
   size_t gws_floats = 0;      // global workspace [workgroup][slot][lane] (lanes <= 0), 0: not allocated
   size_t hull_ws_floats = 0;  // polytope workspace of the hull-hull narrow phase, one block per wavefront of the step grid, 0: not allocated
-  std::vector<int32_t> table;             // PLB | PLL | PD | GD | SD | AM
-  size_t pd_off = 0, gd_off = 0, sd_off = 0, am_off = 0;
+  std::vector<int32_t> table;             // PLB | PLL | PD | GD | SD | AM | RH
+  size_t pd_off = 0, gd_off = 0, sd_off = 0, am_off = 0, rh_off = 0;
   std::vector<int32_t> blob_i;            // device copy of the int blob, with the IK hints in the op flags
   std::vector<float> blob_f;              // the float blob converted once
   MotorTable mt;                          // default velocity motors on every joint

@@ -18,6 +18,7 @@ PlanSwitches plan_switches_from_env() {
 #define X(name, field, doc) if (const char* v = getenv(#name)) { s.field.set = true; s.field.value = atoi(v); }
   DG_PLAN_SWITCHES(X)
 #undef X
+  if (const char* v = getenv("DG_NO_NP_SKIP")) { s.no_np_skip.set = true; s.no_np_skip.value = atoi(v); }  // (beside the table: dg_plan.h)
   return s;
 }
 
@@ -264,6 +265,35 @@ int plan_world(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int 
       plan.push_back((int32_t)m);
     }
   }
+  // rho per link, device-only (np_skip below): for joint i of a serial chain, the largest distance from the joint's origin that any
+  // point of any shape on link i or a later link of the chain can have in any configuration -- over shapes s on link j >= i,
+  // sum_{k = i+1 .. j} |LF_POS_k| + |centre of s in its link frame| + extent of s.  The extent is the bounding radius the narrow
+  // phase uses (SC_BOUND), and for a hull at least the half length of the capsule that contains it (the ends of that capsule are
+  // points the narrow phase measures from).  Rounded up.  A point of the chain then moves by at most sum_i |dq_i| rho_i when the
+  // joints move by dq (revolute joints: each rotates everything behind it about an axis through its origin).  Other bodies: zeros.
+  out.rh_off = plan.size();
+  { const double* SFh = F + I[DG_H_OFF_SHAPE_F]; const double* LFh = F + I[DG_H_OFF_LINK_F];
+    std::vector<float> rho((size_t)nl, 0.f);
+    for (int b = 0; b < nb; b++) {
+      const int32_t* B = BI + b * DG_BI_STRIDE; const int first = B[DG_BI_FIRST_LINK], n = B[DG_BI_N_LINKS];
+      if (!is_fixed(B) || !is_serial_chain(B, LI, 6)) continue;
+      for (int i = 0; i < n; i++) {
+        double best = 0.0, along = 0.0;
+        for (int j = i; j < n; j++) {
+          if (j > i) { const double* lp = LFh + (first + j) * DG_LF_STRIDE + DG_LF_POS; along += std::sqrt(lp[0] * lp[0] + lp[1] * lp[1] + lp[2] * lp[2]); }
+          for (int s = 0; s < I[DG_H_N_SHAPES]; s++) {
+            const int32_t* si = SIh + s * DG_SI_STRIDE; if (si[DG_SI_BODY] != b || si[DG_SI_LINK] != first + j) continue;
+            const double* sf = SFh + s * DG_SF_STRIDE; const int st = si[DG_SI_TYPE];
+            const double p0 = sf[DG_SF_PARAMS], p1 = sf[DG_SF_PARAMS + 1], p2 = sf[DG_SF_PARAMS + 2];
+            const double ext = st == DG_SHAPE_SPHERE ? p0 : st == DG_SHAPE_BOX ? std::sqrt(p0 * p0 + p1 * p1 + p2 * p2)
+                             : st == DG_SHAPE_POINTS ? std::max(std::max(p0 + p1, p2), sf[DG_SF_HULL_HALF]) : p0 + p1;
+            best = std::max(best, along + std::sqrt(sf[DG_SF_POS] * sf[DG_SF_POS] + sf[DG_SF_POS + 1] * sf[DG_SF_POS + 1] + sf[DG_SF_POS + 2] * sf[DG_SF_POS + 2]) + ext);
+          }
+        }
+        rho[(size_t)(first + i)] = (float)(best * (1.0 + 1e-6));
+      }
+    }
+    for (int l = 0; l < nl; l++) { int32_t bits; memcpy(&bits, &rho[(size_t)l], 4); plan.push_back(bits); } }
   PLB = plan.data(); PLL = plan.data() + (size_t)nb * PLB_STRIDE;  // (the appends above may have moved the vector)
   // ---- the scene as the kernels see it
   sc.nba = 0; for (int b = 0; b < nb; b++) if (!(BI[b * DG_BI_STRIDE + DG_BI_FLAGS] & DG_BODY_FROZEN)) sc.nba = b + 1;
@@ -339,6 +369,22 @@ int plan_world(const int32_t* I, int64_t n_i, const double* F, int64_t n_f, int 
       if (code == DG_OP_EXTERNAL_FORCE || code == DG_OP_PROPELLOR || code == DG_OP_ADMITTANCE || (code == DG_OP_JOINT_CONTROL && oi[DG_OI_FLAGS] == DG_JC_TORQUE)) ok = false;
     }
     sc.early_dyn = (ok && long_update) ? 1 : 0;
+  }
+  // Later substeps without narrow phase and pose pass while the clearance lasts (substep_np_skip, dg_solver.h): the four-wavefront
+  // kernel with both narrow-phase wavefronts and the fused contact-free substep, two fixed-base chains of six revolute joints
+  // (rho above bounds rotations only) that are the scene's only moving bodies (nobody else reads a link pose between the
+  // substeps, nothing else can come closer), and a second substep to skip.  The four workspace slots it needs are spare
+  // slots of the padding behind the velocity-change blocks (split_slots), so the LDS plan does not grow.
+  sc.np_skip = 0;
+  if (sc.coll_wave && sc.coll_split && sc.split_pgs > 0 && ncons == 0 && sc.substeps >= 2 && !sw.no_np_skip && sc.total_slots * 64 * 4 <= LDS_MAX) {
+    bool ok = sc.reg_body[0] >= 0 && sc.reg_body[1] == sc.helper_body;
+    for (int k = 0; k < 2 && ok; k++) {
+      const int32_t* B = BI + sc.reg_body[k] * DG_BI_STRIDE; const int first = B[DG_BI_FIRST_LINK];
+      ok = is_fixed(B) && B[DG_BI_N_LINKS] == 6 && PLB[sc.reg_body[k] * PLB_STRIDE + PLB_CHAIN];
+      for (int i = 0; i < 6 && ok; i++) ok = LI[(first + i) * DG_LI_STRIDE + DG_LI_TYPE] == 0;
+    }
+    for (int b = 0; b < nb && ok; b++) if (!is_static(BI + b * DG_BI_STRIDE) && b != sc.reg_body[0] && b != sc.reg_body[1]) ok = false;
+    sc.np_skip = ok ? 1 : 0;
   }
   // ---- default velocity motors on every joint
   memset(&out.mt, 0, sizeof out.mt);

@@ -119,14 +119,30 @@ enum { SC_C = 0, SC_H = 3, SC_R = 6, SC_BOUND = 7, SC_STRIDE = 8 };
 // grouping (lane = env * SLC + sl) -- the SLC lanes of an env do everything identically (same values to the same LDS
 // slots) except the pairs of a group against a box frozen in the world (the ground plane, every wall), which they
 // test SLC at a time, one pair per lane, and then append to the env's list in pair order.
-template <int LANES, int TBL, int SLC = 1>
-DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff, int list = -1, int sl = 0) {
+// CLR (the four-wavefront kernels only; every other instantiation is the code it was): *clear receives, per lane, a lower bound of
+// how far everything the call looked at is from reporting a contact -- the minimum over
+//   a group left out by its bounding test           |dc| - reach
+//   a pair left out by its sphere test              |ca - cb| - reach (the reach of that test, hull margins included)
+//   a hull pair that reaches the containing capsules  the larger of that and |qa - qb| - lim
+//   a round pair that reaches its exact test        dist - margin
+//   anything else (a lane that runs GJK, a box)     0
+// Every term is a distance between points that ride on the bodies (shape centres, ends of segments) minus a constant, so while the
+// two bodies' points have moved by less than `clear` in total, the same call on the new poses reports nothing (substep_np_skip).
+// (a length for the clearance: v_sqrt_f32 as it is, 1 ulp -- the library's correctly rounded sqrtf is ~15 instructions, and two of them
+// per pair put 4.5 k cycles on the narrow-phase wavefronts in the update phase, where they have 2 k to spare; the 1e-4 m of
+// substep_np_skip covers an ulp of 4 m two hundred times)
+DGD float clr_len(float d2) { return __builtin_amdgcn_sqrtf(d2); }
+template <int LANES, int TBL, int SLC = 1, bool CLR = false>
+DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff, int list = -1, int sl = 0, float* clear = nullptr) {
+  static_assert(!CLR || SLC == 1, "the clearance is kept by the one-lane-per-env form only");
   const DevScene& sc = ln.sc; int cnt = 0; const float margin = sc.HF[DG_HF_CONTACT_MARGIN];
+  float clr = 1.0e30f; (void)clr;
+  auto clr_min = [&](float v) { if constexpr (CLR) clr = fminf(clr, v); else (void)v; };
   const bool hull_mode = sc.HF[DG_HF_HULL_CONTACTS] > 0.f; const float hmg = sc.HF[DG_HF_HULL_MARGIN];
   // distance term of the group tests: two hulls that collide as hulls report contacts out to margin + 2 x hull margin
   const float gmargin = margin + (hull_mode ? 2.f * hmg : 0.f);
   if (list < 0) list = sc.cont_off;
-  if (sc.npairs == 0) { ln.L(list) = 0.f; return 0; }
+  if (sc.npairs == 0) { ln.L(list) = 0.f; if constexpr (CLR) *clear = clr; return 0; }
   for (int sh = 0; sh < sc.nsha; sh++) {
     const int type = sc.SI[sh * DG_SI_STRIDE + DG_SI_TYPE]; if (type == DG_SHAPE_BOX) continue;
     WShape w; shape_world(ln, sh, w); V3 e0 = w.p, e1 = w.p;
@@ -161,7 +177,7 @@ DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff
     if (g_first >= pair_hi || g_first + g_count <= pair_lo) continue;
     if (ba != cached_body) { cpos = ln.base_pos(ba); cached_body = ba; }
     if (orr >= 0.f) {  // frozen static partner: everything needed is in the descriptor
-      const V3 dc = cpos - v3(ox, oy, oz); if (!__any(dot(dc, dc) < orr * orr)) continue;
+      const V3 dc = cpos - v3(ox, oy, oz); if (!__any(dot(dc, dc) < orr * orr)) { if constexpr (CLR) clr_min(clr_len(dot(dc, dc)) - orr); continue; }
     } else {
       const int bb = gi[DG_GI_BODY_B], ss = gi[DG_GI_STATIC_SHAPE];
       V3 other; float reach = sc.BF[ba * DG_BF_STRIDE + DG_BF_BOUND] + gmargin;
@@ -172,7 +188,7 @@ DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff
         if (si[DG_SI_FLAGS] & DG_SHAPE_WORLD) other = v3(sf[DG_SF_POS], sf[DG_SF_POS + 1], sf[DG_SF_POS + 2]);
         else { WShape w; shape_world(ln, ss, w); other = w.p; }
       } else { other = ln.base_pos(bb); reach += sc.BF[bb * DG_BF_STRIDE + DG_BF_BOUND]; }
-      { const V3 dc = cpos - other; if (!__any(dot(dc, dc) < reach * reach)) continue; }
+      { const V3 dc = cpos - other; if (!__any(dot(dc, dc) < reach * reach)) { if constexpr (CLR) clr_min(clr_len(dot(dc, dc)) - reach); continue; } }
     }
   const int first = max(g_first, pair_lo), count = min(g_first + g_count, pair_hi) - first;  // this wave's share
   if constexpr (SLC > 1) {
@@ -265,7 +281,9 @@ DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff
       // hull against hull (DG_HF_HULL_CONTACTS, dg_hull.h): the lanes whose bounding spheres reach each other run GJK on the two
       // point sets in their link frames; one contact per pair
       const float reach = cu.reach + 2.f * hmg; const V3 dc = cu.ca - cu.cb; const bool near = dot(dc, dc) < reach * reach;
-      if (!__any(near)) continue;
+      float sphere_clr = 0.f, capsule_clr = 0.f; (void)sphere_clr; (void)capsule_clr;
+      if constexpr (CLR) sphere_clr = clr_len(dot(dc, dc)) - reach;
+      if (!__any(near)) { clr_min(sphere_clr); continue; }
       cip da = sc.SD + 4 * sa, db = sc.SD + 4 * sb;
       auto frame_of = [&](cip sd, M3& Rl, V3& pl) {
         if (sd[0] < 0) { M3 Id = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}}; Rl = Id; pl = v3(0.f, 0.f, 0.f); }
@@ -280,7 +298,9 @@ DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff
         const V3 axa = mul(hp.RA, v3(Rsa.m[2], Rsa.m[5], Rsa.m[8])) * fa[DG_SF_HULL_HALF], axb = mul(hp.RB, v3(Rsb.m[2], Rsb.m[5], Rsb.m[8])) * fb[DG_SF_HULL_HALF];
         V3 qa, qb; seg_seg(cu.ca - axa, cu.ca + axa, cu.cb - axb, cu.cb + axb, qa, qb);
         const float lim = ln.L(oa + SC_R) + ln.L(ob + SC_R) + margin + 2.f * hmg; const V3 dq = qa - qb;
+        if constexpr (CLR) capsule_clr = clr_len(dot(dq, dq)) - lim;
         close = near && dot(dq, dq) < lim * lim; }
+      if constexpr (CLR) clr_min(close ? 0.f : fmaxf(sphere_clr, capsule_clr));  // (a lane that goes on to GJK: no bound)
       if (!__any(close)) continue;
       hp.pa = sc.PF + 3 * da[2]; hp.na = da[3]; hp.pb = sc.PF + 3 * db[2]; hp.nb = db[3]; hp.tBA = plb - pla;
       hp.ew = hull_ws_of(sc.hull_ws);
@@ -312,14 +332,16 @@ DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff
 #endif
     if (tb != DG_SHAPE_BOX) {
       // round vs round: closest points of the two segments, then sphere-sphere
-      { const V3 dc = cu.ca - cu.cb; if (!__any(dot(dc, dc) < cu.reach * cu.reach)) continue; }
+      { const V3 dc = cu.ca - cu.cb; if (!__any(dot(dc, dc) < cu.reach * cu.reach)) { if constexpr (CLR) clr_min(clr_len(dot(dc, dc)) - cu.reach); continue; } }
       const V3 ha = ln.L3(oa + SC_H), hb = ln.L3(ob + SC_H); const float ra = ln.L(oa + SC_R), rb = ln.L(ob + SC_R);
       const V3 a0 = cu.ca - ha, a1 = cu.ca + ha, b0 = cu.cb - hb, b1 = cu.cb + hb;
       V3 ca = a0, cb = b0;
       if (ta == DG_SHAPE_SPHERE && tb != DG_SHAPE_SPHERE) cb = closest_on_seg(b0, b1, a0);
       else if (ta != DG_SHAPE_SPHERE) seg_seg(a0, a1, b0, b1, ca, cb);
-      emit_contact(ln, list, cnt, pi, sphere_sphere(ca, ra, cb, rb, margin), flip);
+      if constexpr (CLR) { const Hit h = sphere_sphere(ca, ra, cb, rb, margin); clr_min(h.dist - margin); emit_contact(ln, list, cnt, pi, h, flip); }
+      else emit_contact(ln, list, cnt, pi, sphere_sphere(ca, ra, cb, rb, margin), flip);
     } else {
+      clr_min(0.f);  // (a box: no bound kept)
       WShape b; shape_world(ln, sb, b);
       const V3 ha = ln.L3(oa + SC_H); const V3 a0 = cu.ca - ha, a1 = cu.ca + ha; const float ra = ln.L(oa + SC_R);
       // cull with the bounding sphere of the round shape against the box
@@ -363,6 +385,7 @@ DGD int collide(const Lane<LANES>& ln, int pair_lo = 0, int pair_hi = 0x7fffffff
   }
   }
   ln.L(list) = (float)cnt;
+  if constexpr (CLR) *clear = clr;
   return cnt;
 }
 
@@ -1880,6 +1903,8 @@ DGD void integrate_body(const Lane<LANES>& ln, int b) {
 // velocity-change blocks (nv_max + 8 slots; readers of that padding only ever multiply it by zero, and these values
 // are finite).
 DGD int split_slots(const DevScene& sc) { return sc.dv_base + sc.nt + sc.nv_max; }
+// (In use: + 0 the sweep count for the diagnostics, + 4 and + 5 the two decision flags.  sc.np_skip takes the other four:)
+enum { NPS_CLEAR = 1 /* + 0 / + 1: the clearance wavefront 2 / 3 measured */, NPS_MOVE0 = 3 /* motion bound of sc.reg_body[0] */, NPS_MOVE1 = 6 /* of sc.helper_body */ };
 
 // Per-substep decision of the helper-wave kernel: are this substep's sweeps split?  The main wave publishes "no
 // contact and no active limit row on my bodies", the helper "no active limit row on my body" (it has just set up its
@@ -2098,6 +2123,36 @@ DGD bool substep_contact_free(const Lane<LANES>& ln) {
   if (sc.coll_split) cnt = fmaxf(cnt, ln.L(sc.cont2_off));
   return !__any(cnt > 0.f);
 }
+// ---- substeps that need no narrow phase (sc.np_skip) -----------------------------------------------------------------------------
+// Two fixed-base arms that are the scene's only moving bodies.  A narrow phase leaves, per env and narrow-phase wavefront, a lower
+// bound `clear` of how far its half of the pair table is from reporting a contact (collide<.., CLR>); the fused substep that follows
+// leaves, per env and arm, d = sum_i |h qn_i| rho_i, an upper bound of how far any point of the arm moves in its integration
+// (fused_free_halves; rho: dg_plan.hip).  A pair's distance shrinks by at most d_A + d_B, so if
+//     min(clear_2, clear_3) > (d_A + d_B) (1 + 2^-10) + 1e-4
+// holds in every env of the workgroup, the next substep's narrow phase would find nothing: it is left out, and with it the pose pass
+// in front of it, whose only reader it is in a fused substep (dynamics_chain reads PLB_R0 and the joint state, the fused pass keeps
+// rows, sweeps and integration in registers, the closing pose pass recomputes every pose for the outputs).  The 1e-4 m covers the
+// rounding of both bounds: positions below 4 m in fp32 through a few dozen operations stay below 1e-5 m.
+// Called by all four wavefronts at the top of substep k >= 1, behind B3 of substep k - 1 and before B1: every wavefront reads the
+// same 64 envs' four slots, so all four reach the same verdict without a barrier (the one product is an explicit fma, so that
+// the four copies cannot round differently).  `prev_fused`: the previous substep took fused_free_halves, so the motion slots are its.
+template <int LANES>
+DGD bool substep_np_skip(const Lane<LANES>& ln, bool prev_fused) {
+  const DevScene& sc = ln.sc;
+  if (!sc.np_skip || !prev_fused) return false;
+  const int xo = split_slots(sc);
+  const float clr = fminf(ln.L(xo + NPS_CLEAR), ln.L(xo + NPS_CLEAR + 1)), d = ln.L(xo + NPS_MOVE0) + ln.L(xo + NPS_MOVE1);
+  return __all(clr > __builtin_fmaf(d, 1.0f + 0x1p-10f, 1e-4f));
+}
+// What narrow-phase wavefront `which` (0 / 1) does between B1 and B2 of a skipped substep: an empty contact list, and the motion
+// comes off its clearance so that a further substep decides on what is left (an executed narrow phase overwrites it).  The motion
+// slots are rewritten by the fused pass behind B2.
+template <int LANES>
+DGD void np_skip_follow(const Lane<LANES>& ln, int which, int list) {
+  const int xo = split_slots(ln.sc);
+  ln.L(list) = 0.f;
+  ln.L(xo + NPS_CLEAR + which) = ln.L(xo + NPS_CLEAR + which) - (ln.L(xo + NPS_MOVE0) + ln.L(xo + NPS_MOVE1));
+}
 // Everything between B2 and B3 for the two arms of such a substep, in the mapping of pgs_reg_halves: wavefront w
 // (0 = main, 1 = helper), lane l serves arm (l >> 5) of env 32 w + (l & 31).  The lane loads its arm's joint state and
 // M^-1 once, forms the motor and limit rows in registers (the expressions of setup_link_rows), runs the motor guess and
@@ -2207,6 +2262,15 @@ DGD void fused_free_halves(const Lane<LANES>& ln, int wave, Prof<PROF>& prof) {
     }
   }
   if (half == 0) col[split_slots(sc) * 64] = (float)iters_done;  // for the diagnostics column, read by the main wave after B3
+  if (sc.np_skip) {  // how far this integration can move any point of the lane's arm (substep_np_skip); every lane, stored or not
+    float dsum = 0.f;  // (|qn| rho summed, then x h: shares no product with the integration above, whose q + h qn stays the fma it was)
+#pragma unroll
+    for (int i = 0; i < RN; i++) {
+      const float r0 = sc.RH[f0 + i], r1 = sc.RH[f1 + i];
+      dsum += fabsf(fminf(fmaxf(qd[i] + rdv[i], -vmax), vmax)) * (half ? r1 : r0);
+    }
+    col[(split_slots(sc) + (half ? NPS_MOVE1 : NPS_MOVE0)) * 64] = h * dsum;
+  }
 }
 
 // ---------------------------------------------------------------- substep
@@ -2218,8 +2282,10 @@ DGD void fused_free_halves(const Lane<LANES>& ln, int wave, Prof<PROF>& prof) {
 // except the dense Gauss-Seidel loop, where they take a share of each env's rows (pgs_dense_sliced).
 // FULLWAVE: every lane of the wavefront is active at the call (step kernels of the 64-lane and global-workspace
 // modes; not the reset kernel, which runs the step under a per-env mask).
+// np_skip (PAR, substep_np_skip): this substep's narrow phase is left out, so the pose pass in front of B1 is too.
+// Returns whether the substep took fused_free_halves.
 template <int LANES, bool PROF, bool PAR = false, bool SLICED = false, bool FULLWAVE = false>
-DGD void substep(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, float* smem = nullptr, float* gws = nullptr, int index = 0) {
+DGD bool substep(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, float* smem = nullptr, float* gws = nullptr, int index = 0, bool np_skip = false) {
   const DevScene& sc = ln.sc; const float h = sc.h; const int hb = PAR ? sc.helper_body : -1;
   const bool primary = SLICED ? (int)threadIdx.x < envs_per_wave(LANES) : true;
   constexpr int LCH = 6;  // links per chunk in the per-link loops
@@ -2238,7 +2304,7 @@ DGD void substep(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, flo
   const Lane<LANES> lq(sc, ln.mt, SLICED ? ln.lds - qlane + qe : ln.lds, SLICED ? ln.st - ln.env + qec : ln.st, SLICED ? qec : ln.env, SLICED ? qvalid : ln.valid);
   if (primary) {
   if (index == sc.substeps - 1 && !early) for (int b = 0; b < sc.nba; b++) if (b != hb) save_prev_velocities(ln, b);
-  if (!early) for (int b = 0; b < sc.nba; b++) if (b != hb) ln.kinematics(b);
+  if (!early && !(PAR && np_skip)) for (int b = 0; b < sc.nba; b++) if (b != hb) ln.kinematics(b);
   }
   if (PAR) __syncthreads();  // B1: every pose is in LDS
   prof.stamp(PS_KIN);
@@ -2555,21 +2621,23 @@ DGD void substep(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, flo
   if constexpr (PAR) {  // fused substep: the sweep counts of envs 32..63 come from the helper wave, hence after B3
     if (fused && diag_out && ln.valid) { iters_done = (int)ln.L(split_slots(sc)); write_diag(); }
   }
+  return fused;
 }
 
 // the helper wave's side of one substep
+// (np_skip: as in substep; returns whether the substep was fused)
 template <int LANES>
-DGD void helper_substep(const Lane<LANES>& ln, bool early, bool last) {
+DGD bool helper_substep(const Lane<LANES>& ln, bool early, bool last, bool np_skip) {
   const DevScene& sc = ln.sc; const int hb = sc.helper_body; Prof<false> none;
   if (last && !early) save_prev_velocities(ln, hb);
-  if (!early) ln.kinematics(hb);
+  if (!early && !np_skip) ln.kinematics(hb);
   __syncthreads();  // B1
   if (!early) {
     ln.template dynamics_chain<6>(hb, none);
     const int dvo = ln.plb(hb)[PLB_DV], nv = ln.plb(hb)[PLB_NV]; for (int k = 0; k < nv; k++) ln.L(dvo + k) = 0.f;
   }
   __syncthreads();  // B2
-  if (substep_contact_free(ln)) { fused_free_halves(ln, 1, none); __syncthreads(); /* B3 */ return; }
+  if (substep_contact_free(ln)) { fused_free_halves(ln, 1, none); __syncthreads(); /* B3 */ return true; }
   uint64_t lm = 0ull, lr = 0ull;
   if (sc.split_pgs) { const int hf = ln.bi(hb)[DG_BI_FIRST_LINK]; setup_link_rows(ln, hf, hf + ln.bi(hb)[DG_BI_N_LINKS], lm, lr); }
   const int hf0 = ln.bi(hb)[DG_BI_FIRST_LINK];
@@ -2579,11 +2647,20 @@ DGD void helper_substep(const Lane<LANES>& ln, bool early, bool last) {
     integrate_body(ln, hb);
   }
   __syncthreads();  // B3
+  return false;
 }
 
 template <int LANES, bool PROF, bool PAR = false, bool SLICED = false, bool FULLWAVE = false>
 DGD void sim_step(const Lane<LANES>& ln, int32_t* diag_out, Prof<PROF>& prof, float* smem = nullptr, float* gws = nullptr) {
   const DevScene& sc = ln.sc;
+  if constexpr (PAR) {  // (the main wave of the four-wavefront kernel)
+    bool fused = false; int skipped = 0;
+    for (int k = 0; k < sc.substeps; k++) {
+      const bool skip = substep_np_skip(ln, fused); skipped += skip ? 1 : 0;
+      fused = substep<LANES, PROF, PAR, SLICED, FULLWAVE>(ln, diag_out, prof, smem, gws, k, skip); prof.stamp(PS_INTEGRATE);
+    }
+    if (sc.skip_count && ln.valid) sc.skip_count[ln.env] = skipped;  // dg_world_set_skip_counter
+  } else
   for (int k = 0; k < sc.substeps; k++) { substep<LANES, PROF, PAR, SLICED, FULLWAVE>(ln, diag_out, prof, smem, gws, k); prof.stamp(PS_INTEGRATE); }
   if (SLICED && (int)threadIdx.x >= envs_per_wave(LANES)) return;
   if (sc.debug_keep_ext) return;

@@ -42,6 +42,10 @@
   //                                               the call below
   //   !pose_ho (any other scene or switch)        the plain order: the wavefront's own pose pass, then `b0` at once
   // `b0` is idempotent, so "again behind" never adds a barrier; see Handover for why its flag is wave-uniform.
+  // sc.np_skip (substep_np_skip, dg_solver.h): every narrow-phase call below keeps its clearance and the wavefront stores it in its own
+  // slot; at the top of a substep k >= 1 all four wavefronts read the same slots and decide alike whether the substep goes without
+  // narrow phase and pose pass.  The barriers of a skipped substep are those of any other: B1, B2, B3.
+  const int clr_slot = split_slots(sc) + NPS_CLEAR;
   const bool pose_ho = sc.early_dyn && sc.coll_split;
   if (wave == 3) {  // ---------------- second half of the narrow phase; in the early first substep, the dynamics of every second moving body
     Lane<64> ln(sc, mt, smem + lane, state + e, e, valid);
@@ -50,15 +54,19 @@
     DG_WAVE_STAMP(0); __syncthreads();  // B0
     if (sc.early_dyn) {  // (round 4: and the second half of the early narrow phase -- the third wavefront alone was 100 k cycles against the update ops' 91 k)
       early_dynamics(ln, 1);
-      if (sc.coll_split) collide<64, 64>(ln, sc.npairs / 2, 0x7fffffff, sc.cont2_off);
+      if (sc.coll_split) { float clr; collide<64, 64, 1, true>(ln, sc.npairs / 2, 0x7fffffff, sc.cont2_off, 0, &clr); ln.L(clr_slot + 1) = clr; }
     }
     DG_WAVE_STAMP(1); __syncthreads();  // B0'
+    bool fused = false;
     for (int k = 0; k < sc.substeps; k++) {
+      const bool skip = substep_np_skip(ln, fused);
       __syncthreads();  // B1
-      if (sc.coll_split && !(sc.early_dyn && k == 0)) collide<64, 64>(ln, sc.npairs / 2, 0x7fffffff, sc.cont2_off);  // (k == 0 with early_dyn: done above)
+      if (skip) np_skip_follow(ln, 1, sc.cont2_off);
+      else if (sc.coll_split && !(sc.early_dyn && k == 0)) { float clr; collide<64, 64, 1, true>(ln, sc.npairs / 2, 0x7fffffff, sc.cont2_off, 0, &clr); ln.L(clr_slot + 1) = clr; }  // (k == 0 with early_dyn: done above)
       __syncthreads();  // B2
       // (a substep without a contact in the workgroup has neither Bq nor Bs: the first two wavefronts run fused_free_halves)
-      if (!substep_contact_free(ln) && split_decide_follow(ln, 0u, false)) __syncthreads();  // Bs: the sweeps run on the first two wavefronts
+      fused = substep_contact_free(ln);
+      if (!fused && split_decide_follow(ln, 0u, false)) __syncthreads();  // Bs: the sweeps run on the first two wavefronts
       __syncthreads();  // B3
     }
     DG_WAVE_STAMP(2); __syncthreads();  // B4: every final pose is in LDS, every state row written
@@ -73,15 +81,19 @@
     if (pose_ho) ln.kinematics(sc.reg_body[0], -1, false);  // the opening poses of the main wave's arm (PLB_R0: the main wave)
     DG_WAVE_STAMP(0); __syncthreads();  // B0
     if (sc.early_dyn) {  // first substep: narrow phase and the arms' dynamics while the first two waves run the update ops
-      collide<64, 64>(ln, 0, sc.coll_split ? sc.npairs / 2 : 0x7fffffff);  // (the fourth wavefront takes every second moving body's dynamics and the other half of the pair table)
+      { float clr; collide<64, 64, 1, true>(ln, 0, sc.coll_split ? sc.npairs / 2 : 0x7fffffff, -1, 0, &clr); ln.L(clr_slot) = clr; }  // (the fourth wavefront takes every second moving body's dynamics and the other half of the pair table)
       early_dynamics(ln, 0);
     }
     DG_WAVE_STAMP(1); __syncthreads();  // B0'
+    bool fused = false;
     for (int k = 0; k < sc.substeps; k++) {
+      const bool skip = substep_np_skip(ln, fused);
       __syncthreads();  // B1: every pose is in LDS
-      if (sc.coll_wave && !(sc.early_dyn && k == 0)) collide<64, 64>(ln, 0, sc.coll_split ? sc.npairs / 2 : 0x7fffffff);  // contact list + count go to LDS; the main wave reads them after B2
+      if (skip) np_skip_follow(ln, 0, sc.cont_off);
+      else if (sc.coll_wave && !(sc.early_dyn && k == 0)) { float clr; collide<64, 64, 1, true>(ln, 0, sc.coll_split ? sc.npairs / 2 : 0x7fffffff, -1, 0, &clr); ln.L(clr_slot) = clr; }  // contact list + count go to LDS; the main wave reads them after B2
       __syncthreads();  // B2
-      if (!substep_contact_free(ln) && split_decide_follow(ln, false, false)) __syncthreads();  // Bs
+      fused = substep_contact_free(ln);
+      if (!fused && split_decide_follow(ln, false, false)) __syncthreads();  // Bs
       __syncthreads();  // B3
     }
     DG_WAVE_STAMP(2); __syncthreads();  // B4
@@ -97,7 +109,8 @@
     if (act_row) run_update_ops(ln, act_row, mask, sc.helper_body, -1, diag, b0);
     b0();  // (no register-chain inverse-kinematics op ran)
     DG_WAVE_STAMP(1); __syncthreads();  // B0'
-    for (int k = 0; k < sc.substeps; k++) helper_substep(ln, sc.early_dyn && k == 0, k == sc.substeps - 1);
+    bool fused = false;
+    for (int k = 0; k < sc.substeps; k++) { const bool skip = substep_np_skip(ln, fused); fused = helper_substep(ln, sc.early_dyn && k == 0, k == sc.substeps - 1, skip); }
     ln.kinematics(sc.helper_body);  // final pose of its body for the outputs
     DG_WAVE_STAMP(2); __syncthreads();  // B4
     // its arm's joint-state observations (state reads only; the main wave skips them)

@@ -592,6 +592,13 @@ enum { DG_DIAG_CONTACTS = 0, DG_DIAG_PGS_ITERS = 1, DG_DIAG_PGS_ITERS_FIRST = 2,
        DG_DIAG_N_IK = 4, DG_DIAG_STRIDE = 8 };
 int32_t dg_world_set_diag_buffer(dg_world* w, int32_t* diag);
 
+/* Skip counter: skipped[num_envs] (int32, device memory) receives with every step, per env, how many of the step's substeps ran
+ * without a narrow phase and the pose pass in front of it because the clearance the previous narrow phase measured exceeded what
+ * the arms could have moved since (plan[DG_PLAN_NP_SKIP]; the decision is the workgroup's, so the 64 envs of a workgroup report
+ * the same number).  Written by the four-wavefront step kernel only (0 where plan[DG_PLAN_NP_SKIP] is 0).  Optional; pass NULL to disable (default).  The buffer must stay
+ * valid until changed. */
+int32_t dg_world_set_skip_counter(dg_world* w, int32_t* skipped);
+
 /* Diagnostic build of the step kernel with in-kernel cycle stamps (s_memtime): when `cycles` is
  * non-NULL, dg_world_step launches the stamped instantiation and lane 0 of every wavefront writes
  * cycles[workgroup][24]: entries 0..11 = shader cycles the (main) wavefront spent in {update ops (IK), kinematics, narrow phase, ABA passes,
@@ -613,11 +620,14 @@ int32_t dg_world_set_profile_buffer(dg_world* w, uint64_t* cycles);
  *                                  1 for a fixed-base serial chain of <= 6 joints;
  *   per link [DG_PLAN_PLL_STRIDE]: slot of the pose (9), of the motor / limit rows (6), of the inertia accumulator (21, inside
  *                                  the transient region) or -1;
- *   then at DG_PLAN_PD_OFF / GD_OFF / SD_OFF / AM_OFF the pair, group and shape descriptors and the ancestor masks. */
+ *   then at DG_PLAN_PD_OFF / GD_OFF / SD_OFF / AM_OFF the pair, group and shape descriptors and the ancestor masks, and at
+ *   DG_PLAN_RH_OFF one float per link: rho, the reach behind the joint that bounds how far a joint increment moves the chain
+ *   (zero for bodies that are not fixed-base serial chains).  DG_PLAN_NP_SKIP: later substeps may skip their narrow phase. */
 enum { DG_PLAN_LANES = 0, DG_PLAN_LDS_BYTES, DG_PLAN_PAR, DG_PLAN_MF, DG_PLAN_TOTAL_SLOTS, DG_PLAN_TR_OFF, DG_PLAN_TR_SLOTS, DG_PLAN_CONT_OFF,
        DG_PLAN_CONT2_OFF, DG_PLAN_NV_MAX, DG_PLAN_NT, DG_PLAN_DENSE, DG_PLAN_CROW_TAIL, DG_PLAN_AB_STRIDE, DG_PLAN_HELPER_BODY, DG_PLAN_REG_BODY0,
        DG_PLAN_REG_BODY1, DG_PLAN_COLL_WAVE, DG_PLAN_COLL_SPLIT, DG_PLAN_SPLIT_PGS, DG_PLAN_EARLY_DYN, DG_PLAN_GWS_FLOATS, DG_PLAN_HULL_WS_FLOATS,
-       DG_PLAN_NBA, DG_PLAN_NSHA, DG_PLAN_PD_OFF, DG_PLAN_GD_OFF, DG_PLAN_SD_OFF, DG_PLAN_AM_OFF, DG_PLAN_TABLE_WORDS, DG_PLAN_COUNT };
+       DG_PLAN_NBA, DG_PLAN_NSHA, DG_PLAN_PD_OFF, DG_PLAN_GD_OFF, DG_PLAN_SD_OFF, DG_PLAN_AM_OFF, DG_PLAN_TABLE_WORDS, DG_PLAN_NP_SKIP,
+       DG_PLAN_RH_OFF, DG_PLAN_COUNT };
 enum { DG_PLAN_PLB_STRIDE = 5, DG_PLAN_PLL_STRIDE = 3 };
 int32_t dg_debug_plan(const int32_t* idata, int64_t n_i, const double* fdata, int64_t n_f, int32_t num_envs, int32_t cu_count,
                       int32_t* plan, int32_t* table, int64_t table_cap);
