@@ -427,7 +427,9 @@ class LqrController(Addon):
     Configs: ``target`` (``[nv]``; default: the pose the reset left -- the model's rest or reset pose), ``q_weight`` (1000; a scalar
     or ``[nv]``), ``qd_weight`` (10; the same), ``torque_weight`` (0.001; the same), ``horizon`` (100), ``relinearize`` (10: the gains
     are recomputed at reset, in ``set_target`` and every that many steps), ``clip_torque`` (yes: the torque is clamped to the URDF
-    effort limits).
+    effort limits), ``riccati`` (``torch``, the default: ``lqr_discretise`` and ``lqr_gain`` below; ``kernel``: ONE stationary
+    ``lq_backward_pass`` launch of ``horizon`` steps, which discretises and iterates in float64 on the device -- the gain is its
+    ``-K[:, 0]``).
 
     The action ``target`` [nv] in ``Box(+-0.05)`` is ADDED to ``q*``; ``set_target(q, mask)`` sets it directly.  Per tick:
     ``calculate_inverse_dynamics(q*, qd=0)`` (the gravity compensation at the target), ``joint_states`` and
@@ -467,6 +469,9 @@ class LqrController(Addon):
         if self.horizon < 1 or self.relinearize < 1:
             raise ValueError('lqr_controller: horizon and relinearize must be >= 1, got %d and %d' % (self.horizon, self.relinearize))
         self.clip_torque = bool(config.get('clip_torque', True))
+        self.riccati = str(config.get('riccati', 'torch'))
+        if self.riccati not in ('torch', 'kernel'):
+            raise ValueError('lqr_controller: riccati must be torch or kernel, got %r' % (self.riccati, ))
         self.torque_limit = [float(j.effort) for j in robot.joints if j.q_index > -1]   # in q_index order
         self.action_space = spaces.Dict(OrderedDict(target=spaces.Box(-0.05, 0.05, shape=(nv, ), dtype='float32')))
         self._ready = False
@@ -522,14 +527,177 @@ class LqrController(Addon):
         tau_g = sim.calculate_inverse_dynamics(self.uid, q=self.q_star, qd=self._zero)
         if self._since is None or self._since >= self.relinearize:
             d = sim.forward_dynamics_derivatives(self.uid, self.q_star, self._zero, tau_g, joint_damping=True, want=('dqdd_dq', 'dqdd_dqd', 'dqdd_dtau'))
-            A, Bm = lqr_discretise(d.dqdd_dq.double(), d.dqdd_dqd.double(), d.dqdd_dtau.double(), float(L.dt), int(L.substeps))
-            self.gain = lqr_gain(A, Bm, self._Q, self._R, self.horizon).float()
+            if self.riccati == 'kernel':
+                Q, R = self._Q.float(), self._R.float()
+                back = sim.lq_backward_pass(self.uid, d.dqdd_dq, d.dqdd_dqd, d.dqdd_dtau, float(L.dt), Q, R, Q, horizon=self.horizon, substeps=int(L.substeps), want=('K', ))
+                self.gain = -back.K[:, 0]
+            else:
+                A, Bm = lqr_discretise(d.dqdd_dq.double(), d.dqdd_dqd.double(), d.dqdd_dtau.double(), float(L.dt), int(L.substeps))
+                self.gain = lqr_gain(A, Bm, self._Q, self._R, self.horizon).float()
             self._since = 0
         self._since += 1
         q, qd = sim.joint_states(self.uid) if state is None else state
         x = torch.cat([q - self.q_star, qd], dim=1)
         tau = tau_g - (self.gain @ x[:, :, None])[:, :, 0]
         sim.apply_joint_torque(self.uid, self._clip(tau) if self.clip_torque else tau)
+
+
+def ilqr_line_search(cost0, costs, status):
+    """``(taken [B] bool, index [B])``: per env the FIRST alpha whose cost ``costs[e, k]`` is below the nominal's ``cost0[e]``; none for an
+    env whose backward pass failed (``status != 0``) or whose costs are not finite."""
+    better = (costs < cost0[:, None]) & (status == 0)[:, None]
+    return better.any(dim=1), better.to(torch.int32).argmax(dim=1)
+
+
+class IlqrController(Addon):
+    """Receding-horizon iLQR in joint space about a joint target ``q*`` that persists per env, written ONLY on the ``env.sim`` query
+    contract: a hook addon, no ``compile()`` op, no counterpart in the reference.  It keeps a torque sequence ``U [B, T, nv]`` and
+    improves it every tick by ``iterations`` iLQR iterations on the arm's own rigid-body model (joint damping on), each four
+    launches: the nominal rollout of ``U`` (``rollout_joint_feedback``, one sample), ``forward_dynamics_derivatives`` at its ``T``
+    points, ``lq_backward_pass`` and ONE ``rollout_joint_feedback`` over all ``line_search`` alphas; the costs are summed in torch and
+    each env takes the FIRST alpha whose cost is below the nominal's, none otherwise.
+
+    Cost: ``sum_t 0.5 (wq |q_t - q*|^2 + wv |qd_t|^2 + wu |u_t - tau_g|^2) + 0.5 (wqT |q_T - q*|^2 + wvT |qd_T|^2)`` with ``tau_g``
+    the gravity compensation at the CURRENT state, recomputed each tick.
+
+    Configs: ``target`` (``[nv]``; default: the pose the reset leaves, as ``lqr_controller``), ``q_weight`` (10), ``qd_weight`` (0.1),
+    ``torque_weight`` (1e-4), ``terminal_q_weight`` (1000), ``terminal_qd_weight`` (10), ``horizon`` (32), ``dt`` (the model's step;
+    default the env step, ``substeps x h``, so that the warm start's shift by one row is exact), ``iterations`` (1), ``line_search``
+    (``[1, 0.5, 0.25, 0.125]``), ``regularization`` (0: the initial ``mu`` added to ``Quu``; an env whose backward pass fails keeps
+    its ``U`` and gets ``max(10 mu, 1e-6)`` for the next tick, and ``mu / 10`` after a success), ``clip_torque`` (yes: the rollouts
+    and the applied torque are clamped to the URDF effort limits).
+
+    The action ``target`` [nv] in ``Box(+-0.05)`` is ADDED to ``q*``; ``set_target(q, mask)`` sets it directly.  Per tick:
+    ``joint_states``, ``calculate_inverse_dynamics(q, 0, 0)``, the iterations, ``apply_joint_torque(U[:, 0])``; then ``U`` shifts by
+    one row, the last row repeated.
+
+    ``reset()`` switches the body's default velocity motors off once and, for the envs in ``env.reset_mask``, puts ``q*`` back at
+    ``target`` (without one: marks it stale, and the first tick after the reset reads it from ``joint_states``, as
+    ``lqr_controller``) and puts their ``U`` back to the gravity compensation on the next tick."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        if not hasattr(parent, 'robot'):
+            raise ValueError('ilqr_controller goes on a model, not on the environment')
+        self.uid = parent.uid
+        robot = parent.robot
+        self.nv = nv = robot.num_dofs
+        if nv < 1:
+            raise ValueError('ilqr_controller: the model has no joints')
+        self.target = None if 'target' not in config else [float(v) for v in config.get('target')]
+        if self.target is not None and len(self.target) != nv:
+            raise ValueError('ilqr_controller: target must have %d elements, got %d' % (nv, len(self.target)))
+        self.q_weight, self.qd_weight, self.torque_weight = float(config.get('q_weight', 10.0)), float(config.get('qd_weight', 0.1)), float(config.get('torque_weight', 1e-4))
+        self.terminal_q_weight, self.terminal_qd_weight = float(config.get('terminal_q_weight', 1000.0)), float(config.get('terminal_qd_weight', 10.0))
+        if min(self.q_weight, self.qd_weight, self.terminal_q_weight, self.terminal_qd_weight) < 0:
+            raise ValueError('ilqr_controller: the state weights must be >= 0')
+        if not self.torque_weight > 0:
+            raise ValueError('ilqr_controller: torque_weight must be > 0')
+        self.horizon, self.iterations = int(config.get('horizon', 32)), int(config.get('iterations', 1))
+        if self.horizon < 1 or self.iterations < 1:
+            raise ValueError('ilqr_controller: horizon and iterations must be >= 1, got %d and %d' % (self.horizon, self.iterations))
+        self.dt = None if 'dt' not in config else float(config.get('dt'))
+        if self.dt is not None and not self.dt > 0:
+            raise ValueError('ilqr_controller: dt must be > 0, got %g' % self.dt)
+        self.line_search = [float(a) for a in config.get('line_search', [1.0, 0.5, 0.25, 0.125])]
+        if not self.line_search or min(self.line_search) <= 0 or max(self.line_search) > 1:
+            raise ValueError('ilqr_controller: line_search must be a list of alphas in (0, 1], got %r' % (self.line_search, ))
+        self.regularization = float(config.get('regularization', 0.0))
+        if self.regularization < 0:
+            raise ValueError('ilqr_controller: regularization must be >= 0, got %g' % self.regularization)
+        self.clip_torque = bool(config.get('clip_torque', True))
+        self.torque_limit = [float(j.effort) for j in robot.joints if j.q_index > -1]   # in q_index order
+        self.action_space = spaces.Dict(OrderedDict(target=spaces.Box(-0.05, 0.05, shape=(nv, ), dtype='float32')))
+        self._ready = False
+
+    def reset(self):
+        env = self.env
+        sim, L = env.sim, env.layout
+        B, nv, T = sim.num_envs, self.nv, self.horizon
+        if not self._ready:
+            first = L.body_first_link[L.resolve_frame(self.uid, -1)[0]]
+            cfg = sim.motor_cfg()
+            cfg[[first + i for i in range(nv)], 2] = 0.0   # the default velocity motors off
+            sim.set_motor_cfg(cfg)
+            new = lambda v: torch.tensor(v, dtype=torch.float32, device=sim.device)
+            self._effort = new(self.torque_limit)
+            if self.dt is None:
+                self.dt = float(L.dt) * int(L.substeps)
+            self._lxx = torch.diag(new([self.q_weight] * nv + [self.qd_weight] * nv))
+            self._luu = torch.diag(new([self.torque_weight] * nv))
+            self._lxx_T = torch.diag(new([self.terminal_q_weight] * nv + [self.terminal_qd_weight] * nv))
+            self._alphas = new(self.line_search)
+            self._zero = torch.zeros((B, nv), dtype=torch.float32, device=sim.device)
+            self.q_star = torch.zeros((B, nv), dtype=torch.float32, device=sim.device)
+            self.U = torch.zeros((B, T, nv), dtype=torch.float32, device=sim.device)
+            self.mu = torch.full((B, ), self.regularization, dtype=torch.float32, device=sim.device)
+            self._stale = torch.zeros((B, 1), dtype=torch.bool, device=sim.device)
+            self._fresh = torch.zeros((B, 1), dtype=torch.bool, device=sim.device)
+            self._any_stale = False
+            self._ready = True
+        rows = torch.ones((B, 1), dtype=torch.bool, device=sim.device) if env.reset_mask is None else torch.as_tensor(env.reset_mask, device=sim.device).reshape(B, 1) != 0
+        if self.target is not None:
+            self.q_star = torch.where(rows, torch.tensor(self.target, dtype=torch.float32, device=sim.device).expand(B, nv), self.q_star)
+        else:   # a hook's reset() runs BEFORE the scene's reset ops: the pose the reset leaves is read on the next tick
+            self._stale = self._stale | rows
+            self._any_stale = True
+        self._fresh = self._fresh | rows   # their U is the gravity compensation of the next tick
+        self.mu = torch.where(rows[:, 0], torch.full_like(self.mu, self.regularization), self.mu)
+
+    def set_target(self, q, mask=None):
+        """The joint target of the envs ``mask`` selects (None: all): ``q`` ``[B, nv]`` or ``[nv]``."""
+        sim = self.env.sim
+        rows = torch.ones((sim.num_envs, 1), dtype=torch.bool, device=sim.device) if mask is None else torch.as_tensor(mask, device=sim.device).reshape(sim.num_envs, 1) != 0
+        self.q_star = torch.where(rows, self.env._as_batch(q, self.nv), self.q_star)
+        self._stale = self._stale & ~rows
+
+    def _cost(self, q0, qd0, q, qd, u, tau_g):
+        """``[B, K]``: the cost of the rollouts ``q, qd, u [B, K, T, nv]`` (states AFTER each step, torques applied) from ``q0, qd0``."""
+        qs, qds = torch.cat([q0[:, None, None, :].expand(-1, q.shape[1], -1, -1), q], dim=2), torch.cat([qd0[:, None, None, :].expand(-1, q.shape[1], -1, -1), qd], dim=2)
+        dq = qs - self.q_star[:, None, None, :]
+        run = (self.q_weight * dq[:, :, :-1].square().sum(dim=(2, 3)) + self.qd_weight * qds[:, :, :-1].square().sum(dim=(2, 3))
+               + self.torque_weight * (u - tau_g[:, None, None, :]).square().sum(dim=(2, 3)))
+        return 0.5 * (run + self.terminal_q_weight * dq[:, :, -1].square().sum(dim=2) + self.terminal_qd_weight * qds[:, :, -1].square().sum(dim=2))
+
+    def _iterate(self, q, qd, tau_g):
+        sim = self.env.sim
+        limit = self._effort if self.clip_torque else None
+        nom = sim.rollout_joint_feedback(self.uid, self.U, q0=q, qd0=qd, dt=self.dt, joint_damping=True, tau_limit=limit, want=('q', 'qd', 'tau'))
+        u = nom.tau[:, 0].clone()
+        cost0 = self._cost(q, qd, nom.q, nom.qd, nom.tau, tau_g)[:, 0]
+        qs, qds = torch.cat([q[:, None], nom.q[:, 0, :-1]], dim=1), torch.cat([qd[:, None], nom.qd[:, 0, :-1]], dim=1)   # the states BEFORE each step
+        d = sim.forward_dynamics_derivatives(self.uid, qs, qds, u, joint_damping=True, want=('dqdd_dq', 'dqdd_dqd', 'dqdd_dtau'))
+        lx = torch.cat([self.q_weight * (qs - self.q_star[:, None, :]), self.qd_weight * qds], dim=2)
+        lu = self.torque_weight * (u - tau_g[:, None, :])
+        lx_T = torch.cat([self.terminal_q_weight * (nom.q[:, 0, -1] - self.q_star), self.terminal_qd_weight * nom.qd[:, 0, -1]], dim=1)
+        back = sim.lq_backward_pass(self.uid, d.dqdd_dq, d.dqdd_dqd, d.dqdd_dtau, self.dt, self._lxx, self._luu, self._lxx_T, lx=lx, lu=lu, lx_T=lx_T, mu=self.mu,
+                                    want=('K', 'k', 'dV'))
+        line = sim.rollout_joint_feedback(self.uid, u, gain=back.K, q_ref=qs, qd_ref=qds, dtau=back.k, alphas=self._alphas, q0=q, qd0=qd, dt=self.dt, joint_damping=True,
+                                          tau_limit=limit, want=('q', 'qd', 'tau'))
+        taken, index = ilqr_line_search(cost0, self._cost(q, qd, line.q, line.qd, line.tau, tau_g), back.status)
+        chosen = line.tau[torch.arange(u.shape[0], device=u.device), index]
+        self.U = torch.where(taken[:, None, None], chosen, u)
+        failed = back.status != 0
+        self.mu = torch.where(failed, (10.0 * self.mu).clamp_min(1e-6), 0.1 * self.mu)
+        self.last = (cost0, taken, index, back.dV.clone(), back.status.clone())   # of the last iteration, for diagnostics
+
+    def update(self, action):
+        env = self.env
+        sim = env.sim
+        q, qd = (t.clone() for t in sim.joint_states(self.uid))
+        if self._any_stale:   # the first tick after a reset: the target of the envs it reset is the pose it left
+            self.q_star = torch.where(self._stale, q, self.q_star)
+            self._stale = torch.zeros_like(self._stale)
+            self._any_stale = False
+        self.q_star = (self.q_star + env._as_batch(action['target'], self.nv)).contiguous()
+        tau_g = sim.calculate_inverse_dynamics(self.uid, q=q, qd=self._zero).clone()
+        self.U = torch.where(self._fresh[:, :, None], tau_g[:, None, :], self.U).contiguous()
+        self._fresh = torch.zeros_like(self._fresh)
+        for _ in range(self.iterations):
+            self._iterate(q, qd, tau_g)
+        torque = self.U[:, 0]
+        self.torque = (torch.where(self._effort > 0, torch.minimum(torch.maximum(torque, -self._effort), self._effort), torque) if self.clip_torque else torque).contiguous()
+        sim.apply_joint_torque(self.uid, self.torque)   # (kept: the torque of the last tick)
+        self.U = torch.cat([self.U[:, 1:], self.U[:, -1:]], dim=1).contiguous()
 
 
 class ExternalForce(_Controller):

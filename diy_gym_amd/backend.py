@@ -76,6 +76,10 @@ SYMBOLS = {
     'dg_world_rollout': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                           ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_dynamics_derivatives': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_rollout_feedback': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                                   ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_lq_backward': (ctypes.c_int32, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
     'dg_world_closest': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -140,6 +144,10 @@ TaskSpaceDynamics = collections.namedtuple('TaskSpaceDynamics', ['jac', 'bias_ac
 JointRollout = collections.namedtuple('JointRollout', ['q', 'qd', 'pos', 'singular'])
 # what forward_dynamics_derivatives returns: device tensors, None for the outputs `want` left out
 DynamicsDerivatives = collections.namedtuple('DynamicsDerivatives', ['qdd', 'dqdd_dq', 'dqdd_dqd', 'dqdd_dtau', 'dtau_dq', 'dtau_dqd', 'singular'])
+# what rollout_joint_feedback returns: device tensors, None for the outputs `want` left out
+FeedbackRollout = collections.namedtuple('FeedbackRollout', ['q', 'qd', 'tau', 'pos', 'singular'])
+# what lq_backward_pass returns: device tensors, None for the outputs `want` left out (status is always there)
+LqBackward = collections.namedtuple('LqBackward', ['K', 'k', 'dV', 'status'])
 LINK_ACCEL_MAX = 16   # DG_LINK_ACCEL_MAX: sensor-frame selectors of one link_accelerations call
 # what link_accelerations returns: [B, n, 3] views of ONE [B, n, 15] buffer, at the columns DG_LA_* of include/diygym_hip.h
 LinkAccelerations = collections.namedtuple('LinkAccelerations', ['lin_acc', 'ang_acc', 'specific_force', 'ang_vel', 'gravity'])
@@ -809,6 +817,146 @@ class HipBackend:
         out = self._dyn_out[key]
         self._dyn_check(self.lib.dg_world_rollout(self.handle, _ptr(self.state), body, frame, (ctypes.c_float * 3)(*lp.tolist()), K, T, dt, int(bool(joint_damping)),
                                                   _ptr(q0), _ptr(qd0), _ptr(tau), *[_ptr(t) for t in out], self._stream()))
+        return out
+
+    def rollout_joint_feedback(self, body, tau, gain=None, q_ref=None, qd_ref=None, dtau=None, alphas=None, q0=None, qd0=None, dt=None, frame=None,
+                               local_pos=(0.0, 0.0, 0.0), joint_damping=False, tau_limit=None, want=('q', 'qd', 'tau')):
+        """``rollout_joint_dynamics`` with the torque of every step formed INSIDE the loop, in ONE launch (``dg_world_rollout_feedback``):
+        the forward pass and line search of iLQR / DDP, and the model evaluation of any time-varying feedback policy.  Sample ``k`` of
+        env ``e`` takes, at the state ``q_t, qd_t`` BEFORE step ``t``, ``tau = tau[e, t] + alphas[k] dtau[e, t] + gain[e, t] @
+        [q_t - q_ref[e, t]; qd_t - qd_ref[e, t]]``, clamped joint by joint to ``+-tau_limit`` where that is ``> 0``.  ``tau``,
+        ``dtau``, ``q_ref``, ``qd_ref`` are ``[B, T, nv]``, ``gain`` ``[B, T, nv, 2 nv]`` (columns ``[q | qd]``; needs both
+        references), ``alphas`` a sequence or ``[K]`` tensor (``K = len(alphas)``, 1 without), ``tau_limit`` ``[nv]``.  A term that is
+        None is absent: with ``tau`` alone the result is ``rollout_joint_dynamics``' of ``tau`` repeated over ``K``, bit for bit.
+        Returns a ``FeedbackRollout``: ``q``, ``qd``, ``tau`` ``[B, K, T, nv]`` (``tau``: the torque applied in step ``t``, after
+        clamping), ``pos`` ``[B, K, T, 3]`` and ``singular`` ``[B, K]``; rows, ``q0``, ``qd0``, ``dt``, ``frame``, ``local_pos``,
+        ``joint_damping`` and ``want`` as ``rollout_joint_dynamics``'.  The tensors are views of buffers kept per ``(want, K, T)``
+        and REUSED by the next call: clone what must last.  ValueError, before anything is launched, for everything the entry
+        refuses and for tensors of the wrong shape, dtype or device."""
+        fields = FeedbackRollout._fields
+        names = list(want)
+        if set(names) - set(fields):
+            raise ValueError('want must name some of %r, got %r' % (fields, want))
+        if 'pos' in names and frame is None:
+            raise ValueError("rollout_joint_feedback: 'pos' in want needs frame")
+        if frame is not None and int(frame) < 0:
+            raise ValueError('frame must be a frame id >= 0, got %d' % int(frame))
+        body, frame, nv = self._dyn_body(body, -1 if frame is None else frame)
+        lp = np.asarray(local_pos, dtype=np.float32).reshape(-1)
+        if lp.size != 3:
+            raise ValueError('local_pos must have 3 elements, got %d' % lp.size)
+        if tau is None:
+            raise ValueError('dg_world_rollout_feedback: tau_ff is NULL')
+        if not isinstance(tau, torch.Tensor) or tau.dim() != 3:
+            raise ValueError('tau must be a torch.Tensor of shape [B, T, nv]')
+        B, T = self.num_envs, int(tau.shape[1])
+        tau = self._require('tau', tau, (B, T, nv), torch.float32)
+        rows = [None if v is None else self._require(name, v, (B, T, nv), torch.float32) for name, v in (('dtau', dtau), ('q_ref', q_ref), ('qd_ref', qd_ref))]
+        gain = None if gain is None else self._require('gain', gain, (B, T, nv, 2 * nv), torch.float32)
+        if alphas is not None and not isinstance(alphas, torch.Tensor):
+            alphas = torch.tensor([float(a) for a in alphas], dtype=torch.float32, device=self.device)
+        K = 1 if alphas is None else int(alphas.numel())
+        if alphas is not None:
+            alphas = self._require('alphas', alphas, (K, ), torch.float32)
+        if tau_limit is not None and not isinstance(tau_limit, torch.Tensor):
+            tau_limit = torch.tensor([float(a) for a in tau_limit], dtype=torch.float32, device=self.device)
+        if tau_limit is not None:
+            tau_limit = self._require('tau_limit', tau_limit, (nv, ), torch.float32)
+        q0, qd0 = self._rows_nv('q0', q0, nv), self._rows_nv('qd0', qd0, nv)
+        dt = float(self.layout.dt if dt is None else dt)
+        key = ('rollout_feedback', body, K, T, tuple(f in names for f in fields))
+        fresh = key not in self._dyn_out
+        if fresh:
+            shapes = {'q': (B, K, T, nv), 'qd': (B, K, T, nv), 'tau': (B, K, T, nv), 'pos': (B, K, T, 3), 'singular': (B, K)}
+            self._dyn_out[key] = FeedbackRollout(*[torch.zeros(shapes[f], dtype=torch.int32 if f == 'singular' else torch.float32, device=self.device)
+                                                   if f in names else None for f in fields])
+        out = self._dyn_out[key]
+        try:
+            self._dyn_check(self.lib.dg_world_rollout_feedback(self.handle, _ptr(self.state), body, frame, (ctypes.c_float * 3)(*lp.tolist()), K, T, dt,
+                                                               int(bool(joint_damping)), _ptr(q0), _ptr(qd0), _ptr(tau), _ptr(rows[0]), _ptr(alphas), _ptr(gain),
+                                                               _ptr(rows[1]), _ptr(rows[2]), _ptr(tau_limit), *[_ptr(t) for t in out], self._stream()))
+        except ValueError:
+            if fresh:   # a refused call keeps no buffers
+                del self._dyn_out[key]
+            raise
+        return out
+
+    def _lq_rows(self, name, v, tail):
+        """``v`` for ``lq_backward_pass``: a float32 tensor on this device whose trailing dimensions are ``tail``, as ``[B, P, *tail]``
+        (a view; ``tail`` alone is one for every env and step, ``[B, *tail]`` one per env)."""
+        if not isinstance(v, torch.Tensor):
+            raise ValueError('%s must be a torch.Tensor, got %s' % (name, type(v).__name__))
+        if v.device != self.device or v.dtype != torch.float32:
+            raise ValueError('%s must be a torch.float32 tensor on %s, got %s on %s' % (name, self.device, v.dtype, v.device))
+        k, B = len(tail), self.num_envs
+        if tuple(v.shape[v.dim() - k:]) != tuple(tail) or v.dim() - k > 2 or (v.dim() - k >= 1 and v.shape[0] != B):
+            raise ValueError('%s must have shape %s, [B = %d] + that or [B, P] + that, got %s' % (name, tuple(tail), B, tuple(v.shape)))
+        if v.dim() == k:
+            return v.expand((B, 1) + tuple(tail))
+        return v.unsqueeze(1) if v.dim() == k + 1 else v
+
+    def lq_backward_pass(self, body, A_q, A_v, Minv, dt, lxx, luu, lxx_T, lx=None, lu=None, lx_T=None, mu=None, horizon=None, substeps=1, want=('K', 'k', 'dV')):
+        """The Riccati / iLQR backward pass of the body's joint-space model for every env in ONE launch (``dg_world_lq_backward``),
+        computed in float64 from float32 tensors.  ``A_q``, ``A_v``, ``Minv`` are the CONTINUOUS derivatives exactly as
+        ``forward_dynamics_derivatives(..., want=('dqdd_dq', 'dqdd_dqd', 'dqdd_dtau'))`` returns them: ``[B, T, nv, nv]`` along a
+        trajectory, or ``[B, nv, nv]`` / ``[B, 1, nv, nv]`` for the stationary case, where ``horizon`` gives ``T``.  The kernel forms
+        ``A, B`` itself over ``substeps`` substeps of ``dt`` (``lqr_discretise``'s formulas).  Running cost ``lxx`` (``m x m``,
+        ``m = 2 nv``, state ``[dq; qd]``), ``luu`` (``nv x nv``), gradients ``lx``, ``lu`` (None = zero), terminal ``lxx_T``, ``lx_T``;
+        each as one matrix / vector for every env and step, one per env (``[B, ..]``) or one per env and step (``[B, T, ..]``; not the
+        terminal ones).  ``mu`` (a number or ``[B]``) is added to the diagonal of ``Quu`` before the solves.  Returns an
+        ``LqBackward``: ``K [B, T, nv, m]``, ``k [B, T, nv]`` -- the update is ``du = alpha k + K dx``, so an LQR gain is
+        ``-K[:, 0]`` -- ``dV [B, 2]`` (the predicted change of cost is ``alpha dV[0] + alpha^2 dV[1]``) and ``status [B]`` int32:
+        0, or ``t + 1`` of the first step whose ``Quu + mu I`` was not positive definite; that env's ``K``, ``k``, ``dV`` are then
+        zeros -- raise its ``mu`` and call again.  Fields not in ``want`` are None (``status`` is always there).  Buffers kept per
+        ``(body, want, T)`` and REUSED by the next call: clone what must last.  ValueError, before anything is launched, for
+        everything the entry refuses and for tensors of the wrong shape, dtype or device."""
+        fields = LqBackward._fields
+        names = list(want) + ['status']
+        if set(names) - set(fields):
+            raise ValueError('want must name some of %r, got %r' % (fields[:3], want))
+        body, _, nv = self._dyn_body(body)
+        B, m = self.num_envs, 2 * nv
+        dyn = [self._lq_rows(name, v, (nv, nv)) for name, v in (('A_q', A_q), ('A_v', A_v), ('Minv', Minv))]
+        if any(t.dim() != dyn[0].dim() or t.shape[1] != dyn[0].shape[1] for t in dyn) or A_q.dim() < 3:
+            raise ValueError('lq_backward_pass: A_q, A_v and Minv must all be [B, nv, nv] or all [B, P, nv, nv], got %s'
+                             % ', '.join(str(tuple(v.shape)) for v in (A_q, A_v, Minv)))
+        P = int(dyn[0].shape[1])
+        T = int(horizon) if horizon is not None else P
+        if P != 1 and P != T:
+            raise ValueError('dg_world_lq_backward: P must be 1 or T = %d, got %d' % (T, P))
+        cost = [None if v is None else self._lq_rows(name, v, tail) for name, v, tail in (('lxx', lxx, (m, m)), ('luu', luu, (nv, nv)), ('lx', lx, (m, )), ('lu', lu, (nv, )))]
+        if cost[0] is None or cost[1] is None or lxx_T is None:
+            raise ValueError('dg_world_lq_backward: lxx, luu and lxx_T are required')
+        PC = max(int(t.shape[1]) for t in cost if t is not None)
+        if PC != 1 and PC != T:
+            raise ValueError("dg_world_lq_backward: the cost's P must be 1 or T = %d, got %d" % (T, PC))
+        for name, t in zip(('lxx', 'luu', 'lx', 'lu'), cost):
+            if t is not None and t.shape[1] not in (1, PC):
+                raise ValueError('lq_backward_pass: %s has %d points per env, the other cost terms %d' % (name, t.shape[1], PC))
+        cost = [None if t is None else t.expand((B, PC) + tuple(t.shape[2:])).contiguous() for t in cost]
+        term = [None if v is None else self._lq_rows(name, v, tail) for name, v, tail in (('lxx_T', lxx_T, (m, m)), ('lx_T', lx_T, (m, )))]
+        if any(t is not None and (t.shape[1] != 1 or v.dim() > len(t.shape) - 1) for t, v in zip(term, (lxx_T, lx_T))):
+            raise ValueError('lq_backward_pass: lxx_T and lx_T are one per env ([m, m] / [m] or [B, ..])')
+        term = [None if t is None else t.contiguous() for t in term]
+        dyn = [t.contiguous() for t in dyn]
+        if mu is not None:
+            if not isinstance(mu, torch.Tensor):
+                mu = torch.full((B, ), float(mu), dtype=torch.float32, device=self.device)
+            mu = self._require('mu', mu, (B, ), torch.float32)
+        key = ('lq_backward', body, T, tuple(f in names for f in fields))
+        fresh = key not in self._dyn_out
+        if fresh:
+            shapes = {'K': (B, T, nv, m), 'k': (B, T, nv), 'dV': (B, 2), 'status': (B, )}
+            self._dyn_out[key] = LqBackward(*[torch.zeros(shapes[f], dtype=torch.int32 if f == 'status' else torch.float32, device=self.device)
+                                              if f in names else None for f in fields])
+        out = self._dyn_out[key]
+        try:
+            self._dyn_check(self.lib.dg_world_lq_backward(self.handle, body, T, P, PC, int(substeps), float(dt), *[_ptr(t) for t in dyn], *[_ptr(t) for t in cost],
+                                                          *[_ptr(t) for t in term], _ptr(mu), *[_ptr(t) for t in out], self._stream()))
+        except ValueError:
+            if fresh:   # a refused call keeps no buffers
+                del self._dyn_out[key]
+            raise
         return out
 
     def rollout_grid(self, K):

@@ -24,6 +24,7 @@
 #include "dg_taskq.h"
 #include "dg_fdq.h"
 #include "dg_ddq.h"
+#include "dg_lqr.h"
 
 using namespace dg;
 
@@ -847,6 +848,38 @@ int32_t dg_world_rollout(dg_world* w, const float* state, int32_t body, int32_t 
                      q0, qd0, tau, q_out, qd_out, pos_out, singular, w->d_gws);
 }
 
+// dg_world_rollout with the torque formed in the loop: feed-forward + alpha x direction + time-varying state feedback, clamped
+int32_t dg_world_rollout_feedback(dg_world* w, const float* state, int32_t body, int32_t frame, const float* local_pos, int32_t K, int32_t T, float dt,
+                                  int32_t joint_damping, const float* q0, const float* qd0, const float* tau_ff, const float* dtau, const float* alpha,
+                                  const float* gain, const float* q_ref, const float* qd_ref, const float* tau_limit,
+                                  float* q_out, float* qd_out, float* tau_out, float* pos_out, int32_t* singular, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_rollout_feedback")) return rc;
+  if (K < 1) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: K must be >= 1, got %d", K);
+  if (T < 1) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: T must be >= 1, got %d", T);
+  if (!std::isfinite(dt) || !(dt > 0.f)) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: dt must be finite and > 0, got %g", (double)dt);
+  if (!tau_ff) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: tau_ff is NULL");
+  if (dtau && !alpha) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: dtau needs alpha");
+  if (gain && (!q_ref || !qd_ref)) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: gain needs q_ref and qd_ref");
+  if (!q_out && !qd_out && !tau_out && !pos_out && !singular) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: every output is NULL");
+  const int n = body_row(w, body)[DG_BI_N_LINKS];
+  {  // B K T n floats of an output and B T n 2n of the gain stay addressable in bytes
+    const int64_t lim = INT64_MAX / 4; int64_t v = w->num_envs;
+    for (const int64_t f : {(int64_t)K, (int64_t)T, (int64_t)n}) { if (v > lim / f) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: %d envs x K %d x T %d x %d joints is beyond INT64_MAX / 4 values", w->num_envs, K, T, n); v *= f; }
+    v = w->num_envs;
+    for (const int64_t f : {(int64_t)T, (int64_t)n, (int64_t)2 * n}) { if (v > lim / f) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: gain of %d envs x T %d x %d x %d is beyond INT64_MAX / 4 values", w->num_envs, T, n, 2 * n); v *= f; }
+  }
+  int gf = -1; float lp[3] = {0.f, 0.f, 0.f};
+  if (pos_out) {
+    if (!local_pos) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: local_pos is NULL (three host floats)");
+    if (frame < 0) return fail(DG_ERR_ARG, "dg_world_rollout_feedback: frame %d out of range (the base of a fixed body does not move)", frame);
+    if (const int rc = frame_check(w, body, frame, &gf, "dg_world_rollout_feedback")) return rc;
+    lp[0] = local_pos[0]; lp[1] = local_pos[1]; lp[2] = local_pos[2];
+  }
+  if (fdq_slots(n) > w->sc.tr_slots) return slots_refusal(w, body, fdq_slots(n), "dg_world_rollout_feedback");
+  return launch_grid(w, dim3(rollout_grid(w, K)), stream, &LaunchTable::rollout_feedback, state, body, gf, lp[0], lp[1], lp[2], (int)K, (int)T, dt,
+                     joint_damping != 0 ? 1 : 0, q0, qd0, tau_ff, dtau, alpha, gain, q_ref, qd_ref, tau_limit, q_out, qd_out, tau_out, pos_out, singular, w->d_gws);
+}
+
 // diagnostics: the workgroups dg_world_rollout would launch for K samples per env (tests: the cap of the global-workspace modes);
 // not part of the public header
 int32_t dg_debug_rollout_grid(const dg_world* w, int32_t K) {
@@ -869,6 +902,34 @@ int32_t dg_world_dynamics_derivatives(dg_world* w, const float* state, int32_t b
   if (ddq_slots(n) > w->sc.tr_slots) return slots_refusal(w, body, ddq_slots(n), "dg_world_dynamics_derivatives");
   return launch_grid(w, dim3(rollout_grid(w, P)), stream, &LaunchTable::dynamics_derivatives, state, body, (int)P, q, qd, tau, joint_damping != 0 ? 1 : 0,
                      qdd, dqdd_dq, dqdd_dqd, dqdd_dtau, dtau_dq, dtau_dqd, singular, w->d_gws);
+}
+
+// ------------------------------------------------------------------ Riccati / iLQR backward pass (dg_lqr.h)
+int32_t dg_world_lq_backward(dg_world* w, int32_t body, int32_t T, int32_t P, int32_t PC, int32_t substeps, double dt,
+                             const float* A_q, const float* A_v, const float* Minv, const float* lxx, const float* luu, const float* lx, const float* lu,
+                             const float* lxx_T, const float* lx_T, const float* mu, float* K_out, float* k_out, float* dV, int32_t* status, void* stream) {
+  if (!w) return fail(DG_ERR_ARG, "dg_world_lq_backward: null argument");
+  if (const int rc = body_check(w, body, "dg_world_lq_backward")) return rc;
+  const int n = body_row(w, body)[DG_BI_N_LINKS];
+  if (n < 1) return fail(DG_ERR_ARG, "dg_world_lq_backward: body %d has no joints", body);
+  if (n > LQ_MAX_JOINTS) return fail(DG_ERR_ARG, "dg_world_lq_backward: body %d has %d joints, the backward pass takes at most %d", body, n, LQ_MAX_JOINTS);
+  if (T < 1) return fail(DG_ERR_ARG, "dg_world_lq_backward: T must be >= 1, got %d", T);
+  if (P != 1 && P != T) return fail(DG_ERR_ARG, "dg_world_lq_backward: P must be 1 or T = %d, got %d", T, P);
+  if (PC != 1 && PC != T) return fail(DG_ERR_ARG, "dg_world_lq_backward: the cost's P must be 1 or T = %d, got %d", T, PC);
+  if (substeps < 1) return fail(DG_ERR_ARG, "dg_world_lq_backward: substeps must be >= 1, got %d", substeps);
+  if (!std::isfinite(dt) || !(dt > 0.0)) return fail(DG_ERR_ARG, "dg_world_lq_backward: dt must be finite and > 0, got %g", dt);
+  if (!A_q || !A_v || !Minv) return fail(DG_ERR_ARG, "dg_world_lq_backward: A_q, A_v and Minv are required");
+  if (!lxx || !luu || !lxx_T) return fail(DG_ERR_ARG, "dg_world_lq_backward: lxx, luu and lxx_T are required");
+  if (!status) return fail(DG_ERR_ARG, "dg_world_lq_backward: status is NULL");
+  {  // B T m m floats stay addressable in bytes
+    const int64_t lim = INT64_MAX / 4; int64_t v = w->num_envs;
+    for (const int64_t f : {(int64_t)T, (int64_t)2 * n, (int64_t)2 * n}) { if (v > lim / f) return fail(DG_ERR_ARG, "dg_world_lq_backward: %d envs x T %d x %d x %d is beyond INT64_MAX / 4 values", w->num_envs, T, 2 * n, 2 * n); v *= f; }
+  }
+  DG_ON_DEVICE(w->device);
+  const LqArgs a = {n, (int)T, (int)P, (int)PC, (int)substeps, dt, A_q, A_v, Minv, lxx, luu, lx, lu, lxx_T, lx_T, mu, K_out, k_out, dV, status};
+  hipLaunchKernelGGL(lq_backward_kernel, dim3((unsigned)w->num_envs), dim3(64), sizeof(double) * (size_t)lq_lds_doubles(n), (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return DG_OK;
 }
 
 // ------------------------------------------------------------------ closest-points query (dg_closestq.h)

@@ -194,4 +194,68 @@ __global__ __launch_bounds__(64) void rollout_kernel(DevScene sc, MotorTable mt,
   }
 }
 
+// rollout_kernel's frame (items, grid stride, workspace column, no cross-lane operation, size_t indices) with the torque of step t
+// formed inside the loop from the state BEFORE the step:
+//   tau = tau_ff[e][t] + alpha[k] dtau[e][t] + gain[e][t] . [q - q_ref[e][t]; qd - qd_ref[e][t]],  clamped to +-tau_limit[i] where that is > 0.
+// tau_ff, dtau, q_ref, qd_ref [num_envs][T][n]; gain [num_envs][T][n][2 n] row-major, columns [q | qd]; alpha [K]; tau_limit [n].
+// dtau (with alpha), gain (with q_ref, qd_ref) and tau_limit are nullable: the term is then absent, not zero, so the torque of a
+// call without them is tau_ff to the bit.  The products are rounded one by one (no fused multiply-add across a term), so that
+// tau_ff + alpha dtau is what the caller's own arithmetic gives.  The feedback sum reads q, qd from their kept slots and the gain
+// row from global memory: fdq_slots(n) as for rollout_kernel.  Row t of tau_out is the torque applied in step t, after clamping;
+// q_out, qd_out, pos_out, singular as rollout_kernel's.
+template <int LANES>
+__global__ __launch_bounds__(64) void rollout_feedback_kernel(DevScene sc, MotorTable mt, float* state, int body, int frame, float lx, float ly, float lz, int K, int T,
+                                                               float dt, int damp, const float* q0, const float* qd0, const float* tau_ff, const float* dtau,
+                                                               const float* alpha, const float* gain, const float* q_ref, const float* qd_ref, const float* tau_limit,
+                                                               float* q_out, float* qd_out, float* tau_out, float* pos_out, int32_t* singular, float* gws) {
+  extern __shared__ float smem[];
+  constexpr int ACTIVE = envs_per_wave(LANES);
+  const int lane = threadIdx.x; if (lane >= ACTIVE) return;
+  float* const ws = workspace_of<LANES>(sc, smem, gws, lane);  // this workgroup's and lane's column, for every item of the loop
+  const size_t items = (size_t)sc.num_envs * (size_t)K;
+  for (size_t item = (size_t)blockIdx.x * ACTIVE + lane; item < items; item += (size_t)gridDim.x * ACTIVE) {
+    const int env = (int)(item / (size_t)K);
+    Lane<LANES> ln(sc, mt, ws, state + env, env, false);  // env's state, read-only: its mass_scale applies
+    const int first = ln.bi(body)[DG_BI_FIRST_LINK], n = ln.bi(body)[DG_BI_N_LINKS];
+    const int qo = sc.tr_off, vo = qo + n, xo = vo + n, blk = xo + n;
+    dq_stage(ln, first, n, q0, DG_LS_Q, qo); dq_stage(ln, first, n, qd0, DG_LS_QD, vo);
+    ln.kinematics(body, qo);
+    const float a = dtau ? alpha[item - (size_t)env * (size_t)K] : 0.f;
+    bool sing = false;
+    for (int t = 0; t < T; t++) {
+      const size_t row = item * (size_t)T + (size_t)t, erow = ((size_t)env * (size_t)T + (size_t)t) * (size_t)n;
+      float* ur = tau_out ? tau_out + row * (size_t)n : nullptr;
+      for (int i = 0; i < n; i++) {  // q, qd stay in their slots; the torque goes to xo
+        float u = tau_ff[erow + i];
+        if (dtau) u = __fadd_rn(u, __fmul_rn(a, dtau[erow + i]));
+        if (gain) {
+          const float* g = gain + (erow + (size_t)i) * (size_t)(2 * n);
+          float s = 0.f;
+          for (int j = 0; j < n; j++) s = __fadd_rn(s, __fmul_rn(g[j], ln.L(qo + j) - q_ref[erow + j]));
+          for (int j = 0; j < n; j++) s = __fadd_rn(s, __fmul_rn(g[n + j], ln.L(vo + j) - qd_ref[erow + j]));
+          u = __fadd_rn(u, s);
+        }
+        if (tau_limit) { const float lim = tau_limit[i]; if (lim > 0.f) u = fminf(fmaxf(u, -lim), lim); }
+        ln.L(xo + i) = u;
+        if (ur) ur[i] = u;
+      }
+      sing = fq_solve(ln, body, first, n, vo, xo, blk, damp != 0) || sing;
+      float* qr = q_out ? q_out + row * (size_t)n : nullptr; float* vr = qd_out ? qd_out + row * (size_t)n : nullptr;
+      for (int i = 0; i < n; i++) {  // semi-implicit, the step's order
+        const float v = ln.L(vo + i) + dt * ln.L(xo + i), p = ln.L(qo + i) + dt * v;
+        ln.L(vo + i) = v; ln.L(qo + i) = p;
+        if (vr) vr[i] = v;
+        if (qr) qr[i] = p;
+      }
+      if (t + 1 < T || pos_out) ln.kinematics(body, qo);  // the next step's pass; after the last step only for pos
+      if (pos_out) {
+        V3 fp, fv, fw; Q4 fq; ln.frame_state(body, frame, true, fp, fq, fv, fw, false);
+        const V3 pw = fp + mul(qmat(fq), v3(lx, ly, lz));
+        float* o = pos_out + row * 3; o[0] = pw.x; o[1] = pw.y; o[2] = pw.z;
+      }
+    }
+    if (singular) singular[item] = sing ? 1 : 0;
+  }
+}
+
 }  // namespace dg

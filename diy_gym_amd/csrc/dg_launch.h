@@ -61,6 +61,9 @@ struct LaSelectors { int32_t n; float ghat[3]; dg_accel_selector s[DG_LINK_ACCEL
   X(forward_dynamics, int body, const float* q, const float* qd, const float* tau, int damp, float* qdd, int32_t* singular, float* gws) \
   X(rollout, int body, int frame, float lx, float ly, float lz, int K, int T, float dt, int damp, const float* q0, const float* qd0, const float* tau, \
     float* q_out, float* qd_out, float* pos_out, int32_t* singular, float* gws) \
+  X(rollout_feedback, int body, int frame, float lx, float ly, float lz, int K, int T, float dt, int damp, const float* q0, const float* qd0, const float* tau_ff, \
+    const float* dtau, const float* alpha, const float* gain, const float* q_ref, const float* qd_ref, const float* tau_limit, \
+    float* q_out, float* qd_out, float* tau_out, float* pos_out, int32_t* singular, float* gws) \
   /* forward-dynamics derivatives (dg_ddq.h) */ \
   X(dynamics_derivatives, int body, int P, const float* q, const float* qd, const float* tau, int damp, float* qdd, float* dqdd_dq, float* dqdd_dqd, float* dqdd_dtau, \
     float* dtau_dq, float* dtau_dqd, int32_t* singular, float* gws)

@@ -584,6 +584,54 @@ int32_t dg_world_dynamics_derivatives(dg_world* w, const float* state, int32_t b
                                       int32_t joint_damping, float* qdd, float* dqdd_dq, float* dqdd_dqd, float* dqdd_dtau,
                                       float* dtau_dq, float* dtau_dqd, int32_t* singular, void* stream);
 
+/* dg_world_rollout with the torque of every step formed INSIDE the loop from the state BEFORE the step: the forward pass and line
+ * search of iLQR / DDP, and the model evaluation of any time-varying feedback policy (TVLQR tracking, tube MPC), in ONE launch of
+ * num_envs x K work items.  Sample k of env e, step t, at the state q_t, qd_t (t = 0: q0[e], qd0[e], NULL = the env's own):
+ *   tau = tau_ff[e][t] + alpha[k] dtau[e][t] + gain[e][t] . [q_t - q_ref[e][t]; qd_t - qd_ref[e][t]]
+ *   tau = clamp(tau, -tau_limit, +tau_limit)       joint by joint where tau_limit[i] > 0, and only when tau_limit is given
+ *   qdd = dg_world_forward_dynamics(q_t, qd_t, tau);  qd += dt qdd;  q += dt qd
+ *   tau_ff             [num_envs][T][nv], required
+ *   dtau, alpha        [num_envs][T][nv] and [K] (device), nullable: without dtau the alpha term is absent and alpha is not read
+ *   gain               [num_envs][T][nv][2 nv] row-major, columns [q | qd], nullable; with it q_ref, qd_ref [num_envs][T][nv] are required
+ *   tau_limit          [nv] (device), nullable
+ *   q_out, qd_out      [num_envs][K][T][nv], row t the state AFTER step t + 1, as dg_world_rollout's
+ *   tau_out            [num_envs][K][T][nv], row t the torque applied in step t, after clamping
+ *   pos_out, singular  [num_envs][K][T][3], [num_envs][K] int32; frame, local_pos, joint_damping: as dg_world_rollout's
+ * An absent term is absent, not zero: a call without dtau, gain and tau_limit gives dg_world_rollout's bits for tau_ff repeated over
+ * K.  Each product of the torque is rounded on its own (tau_ff + alpha dtau is what fp32 arithmetic outside gives).  Each output may
+ * be NULL, at least one must not be.  DG_ERR_ARG (nothing launched, outputs untouched) for everything dg_world_rollout refuses (tau_ff
+ * in tau's place), dtau without alpha, gain without both references, and num_envs x T x nv x 2 nv beyond INT64_MAX / 4. */
+int32_t dg_world_rollout_feedback(dg_world* w, const float* state, int32_t body, int32_t frame, const float* local_pos, int32_t K, int32_t T,
+                                  float dt, int32_t joint_damping, const float* q0, const float* qd0, const float* tau_ff, const float* dtau,
+                                  const float* alpha, const float* gain, const float* q_ref, const float* qd_ref, const float* tau_limit,
+                                  float* q_out, float* qd_out, float* tau_out, float* pos_out, int32_t* singular, void* stream);
+
+/* The Riccati / iLQR backward pass of the joint-space model of `body` (nv <= 12 joints, m = 2 nv states [dq; qd]), every env in ONE
+ * launch.  It reads nothing of the scene but nv and takes the CONTINUOUS derivatives as dg_world_dynamics_derivatives returns them;
+ * A_t, B_t are formed inside, in float64, over `substeps` substeps of dt with the torque held, the step's semi-implicit order:
+ *   A_h = [[I + dt^2 A_q, dt (I + dt A_v)], [dt A_q, I + dt A_v]], B_h = [[dt^2 Minv], [dt Minv]], A = A_h^s, B = sum_{k<s} A_h^k B_h.
+ * From Vx = lx_T, Vxx = lxx_T, for t = T-1 .. 0:
+ *   Qx = lx + A^T Vx;  Qu = lu + B^T Vx;  Qxx = lxx + A^T Vxx A;  Qux = B^T Vxx A;  Quu = luu + B^T Vxx B
+ *   k = -(Quu + mu I)^-1 Qu;  K = -(Quu + mu I)^-1 Qux     (Cholesky; a pivot <= 0 or not finite is a failure)
+ *   dV += (k . Qu, 0.5 k^T Quu k)
+ *   Vx = Qx + K^T Quu k + K^T Qu + Qux^T k;  Vxx = sym(Qxx + K^T Quu K + K^T Qux + Qux^T K)      (the unregularised Quu)
+ * so the control update is du = alpha k + K dx, and the gain of a stationary LQR is -K_out[:, 0] with lx = lu = 0.  Computed in
+ * float64, read and written as float32, all device arrays:
+ *   A_q, A_v, Minv   [num_envs][P][nv][nv], P == T or P == 1 (the one point at every t)
+ *   lxx, luu         [num_envs][PC][m][m], [num_envs][PC][nv][nv], PC == T or 1; lx [..][m], lu [..][nv], nullable = zero; no lux term
+ *   lxx_T, lx_T      [num_envs][m][m], [num_envs][m] (nullable = zero)
+ *   mu               [num_envs], nullable = 0
+ *   K_out, k_out, dV [num_envs][T][nv][m], [num_envs][T][nv], [num_envs][2], each nullable
+ *   status           [num_envs] int32, required: 0, or t + 1 of the first step whose factorisation failed; that env's K_out, k_out and
+ *                    dV are then all zeros (raise mu and call again).  Nothing is left non-finite or unwritten.
+ * DG_ERR_ARG (nothing launched, outputs untouched) for a NULL world, a body out of range, without joints or with more than 12,
+ * T < 1, P or PC not in {1, T}, substeps < 1, a dt that is not finite or <= 0, a missing required array, and
+ * num_envs x T x m x m beyond INT64_MAX / 4. */
+int32_t dg_world_lq_backward(dg_world* w, int32_t body, int32_t T, int32_t P, int32_t PC, int32_t substeps, double dt,
+                             const float* A_q, const float* A_v, const float* Minv, const float* lxx, const float* luu, const float* lx,
+                             const float* lu, const float* lxx_T, const float* lx_T, const float* mu,
+                             float* K_out, float* k_out, float* dV, int32_t* status, void* stream);
+
 /* Per-env diagnostics of the last step: diag[num_envs][DG_DIAG_STRIDE] (int32), columns DG_DIAG_*: contact count and
  * Gauss-Seidel iterations of the final substep, the same two of the first substep, and the iterations each of the
  * scene's first DG_DIAG_N_IK inverse-kinematics ops ran for that env.  Optional; pass NULL to disable (default).  The
