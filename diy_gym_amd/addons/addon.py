@@ -27,12 +27,12 @@ class AddonFactory:
 
     class _Registry:
         def __init__(self):
-            from .controllers import AdmittanceController, IlqrController, InverseKinematicsController, JointController, ExternalForce, LqrController, MppiController, OperationalSpaceController
+            from .controllers import AdaptiveController, AdmittanceController, IlqrController, InverseKinematicsController, JointController, ExternalForce, LqrController, MppiController, OperationalSpaceController
             from .sensors import Camera, ContactForceSensor, ContactSensor, ForceTorqueSensor, ImuSensor, JointStateSensor, JointWrenchSensor, Lidar, LinkStateSensor, ObjectStateSensor, ProximitySensor
             from .rewards import ReachTarget, ElectricityCost, TimePenalty
             from .misc import DynamicsRandomizer, Respawn, SpawnMultiple, VisualRandomizer
             from .unsupported import StuckJointCost, DrawCoords
-            # the 17 keys of reference addon.py:36-54, and `lidar`, `contact_sensor`, `contact_force_sensor`, `proximity_sensor`, `link_state_sensor`, `joint_wrench_sensor`, `imu_sensor`, `osc_controller`, `mppi_controller`, `lqr_controller` and `ilqr_controller` (no counterpart there)
+            # the 17 keys of reference addon.py:36-54, and `lidar`, `contact_sensor`, `contact_force_sensor`, `proximity_sensor`, `link_state_sensor`, `joint_wrench_sensor`, `imu_sensor`, `osc_controller`, `mppi_controller`, `lqr_controller`, `ilqr_controller` and `adaptive_controller` (no counterpart there)
             self.addons = {
                 'ik_controller': InverseKinematicsController,
                 'joint_controller': JointController,
@@ -62,6 +62,7 @@ class AddonFactory:
                 'mppi_controller': MppiController,
                 'lqr_controller': LqrController,
                 'ilqr_controller': IlqrController,
+                'adaptive_controller': AdaptiveController,
             }
 
     @staticmethod

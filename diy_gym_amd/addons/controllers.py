@@ -542,6 +542,131 @@ class LqrController(Addon):
         sim.apply_joint_torque(self.uid, self._clip(tau) if self.clip_torque else tau)
 
 
+class AdaptiveController(Addon):
+    """The Slotine-Li adaptive controller in joint space about a joint target ``q*`` that persists per env, written ONLY on the
+    ``env.sim`` query contract: a hook addon, no ``compile()`` op, no counterpart in the reference.  It makes ``q`` follow ``q*``
+    WITHOUT knowing the link masses -- what a ``dynamics_randomizer`` varies per env: it holds one mass-scale estimate
+    ``s_hat [B, nv]`` per link, started at 1, against the scene's nominal parameters ``theta0 = inertial_parameters(uid,
+    nominal=True)``, and never reads the env's true masses.  Per tick, with ``dt`` the env step:
+
+        q, qd  = joint_states
+        e      = q - q*;  qd_r = -lambda e;  qdd_r = -lambda qd;  sl = qd - qd_r
+        r      = inverse_dynamics_regressor(q, qd, qdd_r, qd_ref=qd_r, theta=s_hat theta0, s=sl, want=('tau', 'grad'))
+        tau    = r.tau - damping sl                         (clipped to the URDF effort limits when clip_torque)
+        s_hat -= dt adapt_gain sum_k(r.grad[:, l, k] theta0[:, l, k])      then clamped to scale_limits
+        apply_joint_torque(tau)
+
+    -- three launches (and ``theta0``'s one, on the first tick).  ``r.tau = Y theta_hat`` is the Slotine-Li control law's model
+    term ``M_hat qdd_r + C_hat qd_r - G_hat`` and ``r.grad = Y^T sl`` the gradient of the adaptation law, projected on the one scale
+    per link (``theta = s theta0``).
+
+    Configs: ``target`` (``[nv]``; default: the pose the reset left, handled as ``lqr_controller`` does), ``lambda`` (10; a scalar or
+    ``[nv]``), ``damping`` (20; a scalar or ``[nv]``, e.g. ``[100, 100, 50, 10, 10, 5]``), ``adapt_gain`` (0.3; 0 freezes the estimate:
+    a fixed-model computed-torque law), ``scale_limits`` (``[0.05, 20]``), ``reset_estimate`` (yes: the envs of ``env.reset_mask``
+    go back to ``s_hat = 1``), ``clip_torque`` (yes).
+
+    The action ``target`` [nv] in ``Box(+-0.05)`` is ADDED to ``q*``; ``set_target(q, mask)`` sets it directly; ``scale_estimate``
+    is ``s_hat``.  ``reset()`` switches the body's default velocity motors off once.
+
+    The tracking error converges; the estimate need NOT converge to the true scales without persistent excitation -- a parameter
+    the motion does not excite stays where it was (holding a UR5 at a pose, the vertical shoulder-pan link's scale never moves off
+    1).  The step's joint damping and link damping are unmodelled dissipation: they help stability and are not in the regressor."""
+    def __init__(self, parent, config):
+        super().__init__(parent, config)
+        if not hasattr(parent, 'robot'):
+            raise ValueError('adaptive_controller goes on a model, not on the environment')
+        self.uid = parent.uid
+        robot = parent.robot
+        self.nv = nv = robot.num_dofs
+        if nv < 1:
+            raise ValueError('adaptive_controller: the model has no joints')
+
+        def vec(key, default):
+            v = np.asarray(config.get(key, default), dtype=np.float64).reshape(-1)
+            if v.size not in (1, nv):
+                raise ValueError('adaptive_controller: %s must be a number or have %d elements, got %d' % (key, nv, v.size))
+            return np.broadcast_to(v, (nv, )).copy()
+        self.target = None if 'target' not in config else [float(v) for v in config.get('target')]
+        if self.target is not None and len(self.target) != nv:
+            raise ValueError('adaptive_controller: target must have %d elements, got %d' % (nv, len(self.target)))
+        self.lam, self.damping = vec('lambda', 10.0), vec('damping', 20.0)
+        if not self.lam.min() > 0 or self.damping.min() < 0:
+            raise ValueError('adaptive_controller: lambda must be > 0 and damping >= 0')
+        self.adapt_gain = float(config.get('adapt_gain', 0.3))
+        if self.adapt_gain < 0:
+            raise ValueError('adaptive_controller: adapt_gain must be >= 0, got %g' % self.adapt_gain)
+        self.scale_limits = [float(v) for v in config.get('scale_limits', [0.05, 20.0])]
+        if len(self.scale_limits) != 2 or not 0 < self.scale_limits[0] <= 1.0 <= self.scale_limits[1]:
+            raise ValueError('adaptive_controller: scale_limits must be [low, high] with 0 < low <= 1 <= high, got %r' % (self.scale_limits, ))
+        self.reset_estimate = bool(config.get('reset_estimate', True))
+        self.clip_torque = bool(config.get('clip_torque', True))
+        self.torque_limit = [float(j.effort) for j in robot.joints if j.q_index > -1]   # in q_index order
+        self.action_space = spaces.Dict(OrderedDict(target=spaces.Box(-0.05, 0.05, shape=(nv, ), dtype='float32')))
+        self._ready = False
+
+    def reset(self):
+        env = self.env
+        sim, L = env.sim, env.layout
+        B, nv = sim.num_envs, self.nv
+        if not self._ready:
+            first = L.body_first_link[L.resolve_frame(self.uid, -1)[0]]
+            cfg = sim.motor_cfg()
+            cfg[[first + i for i in range(nv)], 2] = 0.0   # the default velocity motors off
+            sim.set_motor_cfg(cfg)
+            self._effort = torch.tensor(self.torque_limit, dtype=torch.float32, device=sim.device)
+            self._lam = torch.tensor(self.lam, dtype=torch.float32, device=sim.device)
+            self._kd = torch.tensor(self.damping, dtype=torch.float32, device=sim.device)
+            self._rate = float(L.dt) * int(L.substeps) * self.adapt_gain
+            self.theta0 = None   # the scene's nominal parameters: read on the first tick (one launch, once)
+            self.q_star = torch.zeros((B, nv), dtype=torch.float32, device=sim.device)
+            self.scale_estimate = torch.ones((B, nv), dtype=torch.float32, device=sim.device)
+            self._stale = torch.zeros((B, 1), dtype=torch.bool, device=sim.device)
+            self._any_stale = False
+            self._ready = True
+        rows = torch.ones((B, 1), dtype=torch.bool, device=sim.device) if env.reset_mask is None else torch.as_tensor(env.reset_mask, device=sim.device).reshape(B, 1) != 0
+        if self.target is not None:
+            self.q_star = torch.where(rows, torch.tensor(self.target, dtype=torch.float32, device=sim.device).expand(B, nv), self.q_star)
+        else:   # a hook's reset() runs BEFORE the scene's reset ops: the pose the reset leaves is read on the next tick
+            self._stale = self._stale | rows
+            self._any_stale = True
+        if self.reset_estimate:
+            self.scale_estimate = torch.where(rows, torch.ones_like(self.scale_estimate), self.scale_estimate)
+
+    def set_target(self, q, mask=None):
+        """The joint target of the envs ``mask`` selects (None: all): ``q`` ``[B, nv]`` or ``[nv]``."""
+        sim = self.env.sim
+        rows = torch.ones((sim.num_envs, 1), dtype=torch.bool, device=sim.device) if mask is None else torch.as_tensor(mask, device=sim.device).reshape(sim.num_envs, 1) != 0
+        self.q_star = torch.where(rows, self.env._as_batch(q, self.nv), self.q_star)
+        self._stale = self._stale & ~rows
+        if mask is None:
+            self._any_stale = False   # (with a mask the flag stays: knowing whether a row is left would cost a device read)
+
+    def _clip(self, tau):
+        return torch.where(self._effort > 0, torch.minimum(torch.maximum(tau, -self._effort), self._effort), tau)
+
+    def update(self, action):
+        env = self.env
+        sim = env.sim
+        if self.theta0 is None:
+            self.theta0 = sim.inertial_parameters(self.uid, nominal=True).clone()
+        q, qd = sim.joint_states(self.uid)
+        if self._any_stale:   # the first tick after a reset: the target of the envs it reset is the pose it left
+            self.q_star = torch.where(self._stale, q, self.q_star)
+            self._stale = torch.zeros_like(self._stale)
+            self._any_stale = False
+        self.q_star = (self.q_star + env._as_batch(action['target'], self.nv)).contiguous()
+        qd_r = (-self._lam * (q - self.q_star)).contiguous()
+        qdd_r = (-self._lam * qd).contiguous()
+        sl = (qd - qd_r).contiguous()
+        theta = (self.scale_estimate[:, :, None] * self.theta0).contiguous()
+        r = sim.inverse_dynamics_regressor(self.uid, q=q, qd=qd, qdd=qdd_r, qd_ref=qd_r, theta=theta, s=sl, want=('tau', 'grad'))
+        tau = r.tau - self._kd * sl
+        if self._rate > 0:
+            step = (r.grad.reshape(-1, self.nv, 10) * self.theta0).sum(dim=2)
+            self.scale_estimate = torch.clamp(self.scale_estimate - self._rate * step, self.scale_limits[0], self.scale_limits[1])
+        sim.apply_joint_torque(self.uid, self._clip(tau) if self.clip_torque else tau)
+
+
 def ilqr_line_search(cost0, costs, status):
     """``(taken [B] bool, index [B])``: per env the FIRST alpha whose cost ``costs[e, k]`` is below the nominal's ``cost0[e]``; none for an
     env whose backward pass failed (``status != 0``) or whose costs are not finite."""

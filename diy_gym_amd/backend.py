@@ -78,6 +78,8 @@ SYMBOLS = {
     'dg_world_dynamics_derivatives': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_rollout_feedback': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                                    ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dg_world_inertial_parameters': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
+    'dg_world_id_regressor': (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_lq_backward': (ctypes.c_int32, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dg_world_closest_scratch_floats': (ctypes.c_int64, [_vp]),
@@ -144,6 +146,8 @@ TaskSpaceDynamics = collections.namedtuple('TaskSpaceDynamics', ['jac', 'bias_ac
 JointRollout = collections.namedtuple('JointRollout', ['q', 'qd', 'pos', 'singular'])
 # what forward_dynamics_derivatives returns: device tensors, None for the outputs `want` left out
 DynamicsDerivatives = collections.namedtuple('DynamicsDerivatives', ['qdd', 'dqdd_dq', 'dqdd_dqd', 'dqdd_dtau', 'dtau_dq', 'dtau_dqd', 'singular'])
+# what inverse_dynamics_regressor returns: device tensors, None for the outputs `want` left out
+DynamicsRegressor = collections.namedtuple('DynamicsRegressor', ['Y', 'tau', 'grad'])
 # what rollout_joint_feedback returns: device tensors, None for the outputs `want` left out
 FeedbackRollout = collections.namedtuple('FeedbackRollout', ['q', 'qd', 'tau', 'pos', 'singular'])
 # what lq_backward_pass returns: device tensors, None for the outputs `want` left out (status is always there)
@@ -1021,6 +1025,67 @@ class HipBackend:
             if fresh:   # a refused call keeps no buffers
                 del self._dyn_out[key]
             raise
+        return out
+
+    # -- inertial parameters and the regressor of the inverse dynamics ---------------------------------------------------------
+    def inertial_parameters(self, body, nominal=False):
+        """The inertial parameters of the body's links for every env (``dg_world_inertial_parameters``): ``[B, nv, 10]``, per link
+        ``[m, m cx, m cy, m cz, Ixx, Ixy, Ixz, Iyy, Iyz, Izz]`` in the link's own frame, ``c`` the centre of mass and ``I`` the inertia
+        about the link-frame origin; a link is a movable joint's child link with everything fixed to it merged.  The env's mass scale
+        (``dynamics_randomizer``) multiplies all ten -- the TRUE parameters, privileged information on the device; ``nominal=True``
+        gives the scene's unscaled values.  ``calculate_inverse_dynamics(q, qd, qdd) = Y(q, qd, qdd) theta`` with
+        ``inverse_dynamics_regressor``'s ``Y``.  The tensor is a buffer kept per ``(body, nominal)`` and REUSED: clone what must last."""
+        body, _, nv = self._dyn_body(body)
+        theta = self._dyn_buf('theta_nominal' if nominal else 'theta', body, self.num_envs, nv, 10)
+        self._dyn_check(self.lib.dg_world_inertial_parameters(self.handle, _ptr(self.state), body, int(bool(nominal)), _ptr(theta), self._stream()))
+        return theta
+
+    def inverse_dynamics_regressor(self, body, q=None, qd=None, qdd=None, qd_ref=None, theta=None, s=None, want=('Y', )):
+        """The regressor of the inverse dynamics for every env, at ``P`` points per env, in ONE launch (``dg_world_id_regressor``):
+        ``tau = Y(q, qd, qdd) theta`` with ``theta`` as ``inertial_parameters`` orders it.  With ``qd_ref`` it is the Slotine-Li form
+        ``Y theta = M qdd + C(q, qd) qd_ref - G`` (``Mdot - 2 C`` skew-symmetric).  Returns a ``DynamicsRegressor``: ``Y``
+        ``[B, (P,) nv, 10 nv]``; ``tau = Y theta`` ``[B, (P,) nv]`` and ``grad = Y^T s`` ``[B, (P,) 10 nv]``, both formed without ``Y``
+        in O(nv).  ``q``, ``qd``, ``qdd``, ``qd_ref`` and ``s`` are ``[nv]``, ``[B, nv]`` or ``[B, P, nv]`` (all given inputs must
+        agree on ``P``); ``q`` / ``qd`` default to each env's current values, ``qdd`` to zero, ``qd_ref`` to ``qd``.  ``theta`` is
+        ``[10 nv]``, ``[B, 10 nv]`` or ``[B, nv, 10]``: per env, never per point -- the caller's estimate; the env's own masses do not
+        enter.  ``'tau'`` in ``want`` needs ``theta`` and ``'grad'`` needs ``s``.  Fields not in ``want`` are None and cost nothing.
+        The tensors are buffers kept per ``(body, want, P)`` and REUSED by the next call: clone what must last.  ValueError, before
+        anything is launched, for everything the entry refuses and for tensors of the wrong shape, dtype or device."""
+        fields = DynamicsRegressor._fields
+        names = list(want)
+        if not names or set(names) - set(fields):
+            raise ValueError('want must name some of %r, got %r' % (fields, want))
+        if 'tau' in names and theta is None:
+            raise ValueError("inverse_dynamics_regressor: 'tau' in want needs theta")
+        if 'grad' in names and s is None:
+            raise ValueError("inverse_dynamics_regressor: 'grad' in want needs s")
+        body, _, nv = self._dyn_body(body)
+        args = ('q', 'qd', 'qdd', 'qd_ref', 's')
+        ins = [self._points_nv(name, v, nv) for name, v in zip(args, (q, qd, qdd, qd_ref, s))]
+        given = [(name, P) for name, (t, P) in zip(args, ins) if t is not None]
+        Ps = set(P for _, P in given)
+        if len(Ps) > 1:
+            raise ValueError('inverse_dynamics_regressor: the inputs must agree on the points per env, got %s'
+                             % ', '.join('%s %s' % (name, 'one point [B, nv]' if P is None else 'P = %d' % P) for name, P in given))
+        P = Ps.pop() if Ps else None
+        B, n_pts = self.num_envs, 1 if P is None else P
+        if theta is not None:
+            if isinstance(theta, torch.Tensor) and theta.dim() == 1:
+                theta = self._rows_nv('theta', theta, 10 * nv)
+            elif isinstance(theta, torch.Tensor) and theta.dim() == 3:
+                theta = self._require('theta', theta, (B, nv, 10), torch.float32)
+            else:
+                theta = self._require('theta', theta, (B, 10 * nv), torch.float32)
+        key = ('regq', body, P, tuple(f in names for f in fields))
+        if key not in self._dyn_out:
+            lead = (B, ) if P is None else (B, P)
+            shapes = {'Y': lead + (nv, 10 * nv), 'tau': lead + (nv, ), 'grad': lead + (10 * nv, )}
+            self._dyn_out[key] = DynamicsRegressor(*[torch.zeros(shapes[f], dtype=torch.float32, device=self.device) if f in names else None for f in fields])
+        out = self._dyn_out[key]
+        (q, _), (qd, _), (qdd, _), (qd_ref, _), (s, _) = ins
+        self._dyn_check(self.lib.dg_world_id_regressor(self.handle, _ptr(self.state), body, n_pts, _ptr(q), _ptr(qd), _ptr(qdd), _ptr(qd_ref),
+                                                       _ptr(theta if out.tau is not None else None), _ptr(s if out.grad is not None else None),
+                                                       _ptr(out.Y), _ptr(out.tau), _ptr(out.grad), self._stream()))
         return out
 
     def forward_dynamics_fn(self, body, joint_damping=False):

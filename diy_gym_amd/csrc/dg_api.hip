@@ -24,6 +24,7 @@
 #include "dg_taskq.h"
 #include "dg_fdq.h"
 #include "dg_ddq.h"
+#include "dg_regq.h"
 #include "dg_lqr.h"
 
 using namespace dg;
@@ -902,6 +903,31 @@ int32_t dg_world_dynamics_derivatives(dg_world* w, const float* state, int32_t b
   if (ddq_slots(n) > w->sc.tr_slots) return slots_refusal(w, body, ddq_slots(n), "dg_world_dynamics_derivatives");
   return launch_grid(w, dim3(rollout_grid(w, P)), stream, &LaunchTable::dynamics_derivatives, state, body, (int)P, q, qd, tau, joint_damping != 0 ? 1 : 0,
                      qdd, dqdd_dq, dqdd_dqd, dqdd_dtau, dtau_dq, dtau_dqd, singular, w->d_gws);
+}
+
+// ------------------------------------------------------------------ inertial parameters, inverse-dynamics regressor (dg_regq.h)
+int32_t dg_world_inertial_parameters(dg_world* w, const float* state, int32_t body, int32_t nominal, float* theta, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_inertial_parameters")) return rc;
+  if (!theta) return fail(DG_ERR_ARG, "dg_world_inertial_parameters: theta is NULL");
+  if ((uintptr_t)theta & 7) return fail(DG_ERR_ARG, "dg_world_inertial_parameters: theta must be 8-byte aligned");
+  return launch(w, stream, &LaunchTable::inertial_params, state, body, nominal != 0 ? 1 : 0, theta);
+}
+
+int32_t dg_world_id_regressor(dg_world* w, const float* state, int32_t body, int32_t P, const float* q, const float* qd, const float* qdd,
+                              const float* qd_ref, const float* theta_hat, const float* s, float* Y, float* tau, float* grad, void* stream) {
+  if (const int rc = dynq_check(w, state, body, -1, "dg_world_id_regressor")) return rc;
+  if (P < 1) return fail(DG_ERR_ARG, "dg_world_id_regressor: P must be >= 1, got %d", P);
+  if (!Y && !tau && !grad) return fail(DG_ERR_ARG, "dg_world_id_regressor: every output is NULL");
+  if (tau && !theta_hat) return fail(DG_ERR_ARG, "dg_world_id_regressor: tau needs theta_hat");
+  if (grad && !s) return fail(DG_ERR_ARG, "dg_world_id_regressor: grad needs s");
+  if (((uintptr_t)Y | (uintptr_t)grad) & 7) return fail(DG_ERR_ARG, "dg_world_id_regressor: Y and grad must be 8-byte aligned");
+  const int n = body_row(w, body)[DG_BI_N_LINKS];
+  {  // B P n 10 n floats stay addressable in bytes
+    const int64_t lim = INT64_MAX / 4; int64_t v = w->num_envs;
+    for (const int64_t f : {(int64_t)P, (int64_t)n, (int64_t)10 * n}) { if (v > lim / f) return fail(DG_ERR_ARG, "dg_world_id_regressor: %d envs x P %d x %d x %d is beyond INT64_MAX / 4 values", w->num_envs, P, n, 10 * n); v *= f; }
+  }
+  if (regq_slots(n) > w->sc.tr_slots) return slots_refusal(w, body, regq_slots(n), "dg_world_id_regressor");
+  return launch_grid(w, dim3(rollout_grid(w, P)), stream, &LaunchTable::id_regressor, state, body, (int)P, q, qd, qdd, qd_ref, theta_hat, s, Y, tau, grad, w->d_gws);
 }
 
 // ------------------------------------------------------------------ Riccati / iLQR backward pass (dg_lqr.h)

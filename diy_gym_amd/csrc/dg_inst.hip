@@ -23,6 +23,7 @@
 #include "dg_taskq.h"
 #include "dg_fdq.h"
 #include "dg_ddq.h"
+#include "dg_regq.h"
 #if DG_LANES == 64 && !defined(DG_MANIFOLD)
 #include "dg_closestq.h"
 #endif

@@ -66,7 +66,11 @@ struct LaSelectors { int32_t n; float ghat[3]; dg_accel_selector s[DG_LINK_ACCEL
     float* q_out, float* qd_out, float* tau_out, float* pos_out, int32_t* singular, float* gws) \
   /* forward-dynamics derivatives (dg_ddq.h) */ \
   X(dynamics_derivatives, int body, int P, const float* q, const float* qd, const float* tau, int damp, float* qdd, float* dqdd_dq, float* dqdd_dqd, float* dqdd_dtau, \
-    float* dtau_dq, float* dtau_dqd, int32_t* singular, float* gws)
+    float* dtau_dq, float* dtau_dqd, int32_t* singular, float* gws) \
+  /* inertial parameters, inverse-dynamics regressor (dg_regq.h) */ \
+  X(inertial_params, int body, int nominal, float* theta, float* gws) \
+  X(id_regressor, int body, int P, const float* q, const float* qd, const float* qdd, const float* qd_ref, const float* theta_hat, const float* s, \
+    float* Y, float* tau, float* grad, float* gws)
 
 struct LaunchTable {
   bool has_prof;

@@ -584,6 +584,35 @@ int32_t dg_world_dynamics_derivatives(dg_world* w, const float* state, int32_t b
                                       int32_t joint_damping, float* qdd, float* dqdd_dq, float* dqdd_dqd, float* dqdd_dtau,
                                       float* dtau_dq, float* dtau_dqd, int32_t* singular, void* stream);
 
+/* The inertial parameters of `body`'s links in every env: theta [num_envs][nv][10], per link (joint index l = 0 .. nv-1; a link is a
+ * movable joint's child link with everything fixed to it merged) in the link's OWN frame
+ *   theta_l = [m, m cx, m cy, m cz, Ixx, Ixy, Ixz, Iyy, Iyz, Izz]
+ * with c the centre of mass and I the inertia about the link-frame ORIGIN in link axes.  The env's per-env mass scale (the
+ * dynamics_randomizer's) multiplies all ten; nominal != 0 gives the unscaled values of the scene instead.  theta must be 8-byte
+ * aligned (a link's ten floats leave as 8-byte stores).  DG_ERR_ARG (nothing launched) for what the dynamics queries refuse, a NULL
+ * theta and a theta that is not 8-byte aligned. */
+int32_t dg_world_inertial_parameters(dg_world* w, const float* state, int32_t body, int32_t nominal, float* theta, void* stream);
+
+/* The regressor of the rigid-body inverse dynamics at P points per env, in ONE launch of num_envs x P work items: what parameter
+ * identification, adaptive control and excitation-trajectory design start from.  Inverse dynamics is linear in the inertial
+ * parameters of dg_world_inertial_parameters, theta as [10 nv]:
+ *   dg_world_inverse_dynamics(q, qd, qdd) = Y(q, qd, qdd) theta
+ * and with a reference velocity qd_ref (Slotine-Li)  Y theta = M qdd + C(q, qd) qd_ref - G  with the Christoffel C, so that
+ * Mdot - 2 C is skew-symmetric; the product is symmetric in (qd, qd_ref), and qd_ref = qd is the plain regressor.
+ *   q, qd, qdd, qd_ref [num_envs][P][nv] or NULL = the env's own q and qd, qdd = 0, qd_ref = qd, at every point of that env
+ *   theta_hat          [num_envs][10 nv], per env, nullable
+ *   s                  [num_envs][P][nv], nullable
+ *   Y                  [num_envs][P][nv][10 nv] row-major; the blocks of links a joint does not carry are written as zeros
+ *   tau                [num_envs][P][nv]     Y theta_hat, formed WITHOUT Y by a Newton-Euler pass: O(nv); needs theta_hat
+ *   grad               [num_envs][P][10 nv]  Y^T s, formed WITHOUT Y from the links' virtual twists: O(nv); needs s
+ * Each output may be NULL and then costs nothing; at least one must not be.  The state is read, never written; the env's own masses
+ * do not enter (theta_hat is the caller's).  DG_ERR_ARG (nothing launched, outputs untouched) for what the dynamics queries refuse,
+ * P < 1, every output NULL, tau without theta_hat, grad without s, a Y or grad that is not 8-byte aligned (blocks of ten floats leave
+ * as 8-byte stores), num_envs x P x nv x 10 nv beyond INT64_MAX / 4, and a body whose
+ * pass would need more workspace than the world has (23 nv slots of the transient region). */
+int32_t dg_world_id_regressor(dg_world* w, const float* state, int32_t body, int32_t P, const float* q, const float* qd, const float* qdd,
+                              const float* qd_ref, const float* theta_hat, const float* s, float* Y, float* tau, float* grad, void* stream);
+
 /* dg_world_rollout with the torque of every step formed INSIDE the loop from the state BEFORE the step: the forward pass and line
  * search of iLQR / DDP, and the model evaluation of any time-varying feedback policy (TVLQR tracking, tube MPC), in ONE launch of
  * num_envs x K work items.  Sample k of env e, step t, at the state q_t, qd_t (t = 0: q0[e], qd0[e], NULL = the env's own):
